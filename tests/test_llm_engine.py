@@ -1575,17 +1575,18 @@ def test_prefix_cache_concurrent_and_aborted():
                 pass
 
         outs = await asyncio.gather(*[one(i) for i in range(4)], aborted())
+        # drain cleanup ON the loop: the abort is applied by the engine's
+        # next step(), which only runs while this event loop is alive (when
+        # the four short requests finish before the cancel lands, the engine
+        # is idle and has not stepped yet by the time gather() returns)
+        for _ in range(100):
+            if eng.allocator.available == eng.allocator.num_blocks:
+                break
+            await asyncio.sleep(0.02)
         return outs[:4]
 
     outs = run(main())
     assert all(len(o) == 8 for o in outs)
-    # drain cleanup
-    import time as _time
-
-    for _ in range(100):
-        if eng.allocator.available == eng.allocator.num_blocks:
-            break
-        _time.sleep(0.02)
     assert eng.allocator.available == eng.allocator.num_blocks
 
 
