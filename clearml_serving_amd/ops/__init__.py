@@ -323,12 +323,6 @@ def attention(
     if q.is_cuda:
         ext = _require_ext("attention")
         if ext is not None:
-            # v2 (swapped-QK^T in-register softmax) measures 1.10-1.18x v1
-            # across BERT/llama shapes (profiles/attn_v2_ab.txt);
-            # CMLS_ATTN_V2=0 falls back to v1
-            if os.environ.get("CMLS_ATTN_V2", "1") != "0":
-                return ext.attention_prefill_v2(q, k, v, bool(causal),
-                                                float(scale), seq_lens, bshd)
             return ext.attention_prefill(q, k, v, bool(causal), float(scale),
                                          seq_lens, bshd)
     if bshd:
@@ -377,22 +371,15 @@ def attention_prefill_paged(
 
     fp8 KV: uint8 e4m3 caches + per-token-per-head ``k_scale``/``v_scale``
     float32 [NB, Hkv, BS]; the gfx950 kernel dequantizes while staging tiles
-    to LDS (attention_v2.hip FP8KV)."""
+    to LDS (attention.hip FP8KV)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if q.is_cuda:
         ext = _require_ext("attention_prefill_paged")
         if ext is not None:
-            if os.environ.get("CMLS_ATTN_V2", "1") != "0":
-                return ext.attention_prefill_paged_v2(
-                    q, k_cache, v_cache, block_table, kv_lens, q_lens,
-                    float(scale), k_scale, v_scale)
-            if k_scale is not None:
-                raise RuntimeError("fp8 KV prefill needs the v2 kernel "
-                                   "(CMLS_ATTN_V2=0 set?)")
             return ext.attention_prefill_paged(
                 q, k_cache, v_cache, block_table, kv_lens, q_lens,
-                float(scale))
+                float(scale), k_scale, v_scale)
     if k_scale is not None:
         return attention_prefill_paged(
             q, _dequant_kv_cpu(k_cache, k_scale),

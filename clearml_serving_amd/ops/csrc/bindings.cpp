@@ -30,11 +30,11 @@ void kv_cache_write(torch::Tensor knew, torch::Tensor vnew,
                     c10::optional<torch::Tensor> v_scale);
 torch::Tensor gemm_bf16(torch::Tensor a, torch::Tensor b);
 torch::Tensor skinny_gemm(torch::Tensor a, torch::Tensor w, int64_t variant);
-torch::Tensor attention_prefill_paged(torch::Tensor q, torch::Tensor k_cache,
-                                      torch::Tensor v_cache,
-                                      torch::Tensor block_table,
-                                      torch::Tensor kv_lens,
-                                      torch::Tensor q_lens, double scale);
+torch::Tensor attention_prefill_paged(
+    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+    torch::Tensor block_table, torch::Tensor kv_lens, torch::Tensor q_lens,
+    double scale, c10::optional<torch::Tensor> k_scale,
+    c10::optional<torch::Tensor> v_scale);
 void rope_inplace(torch::Tensor q, torch::Tensor k, torch::Tensor positions,
                   double theta);
 std::vector<torch::Tensor> rmsnorm_fp8(torch::Tensor x, torch::Tensor weight,
@@ -49,15 +49,6 @@ torch::Tensor skinny_gemm_fp8_v2(torch::Tensor a8, torch::Tensor a_scale,
 torch::Tensor conv3x3_nhwc(torch::Tensor x, torch::Tensor w,
                            c10::optional<torch::Tensor> bias, bool relu,
                            c10::optional<torch::Tensor> residual);
-torch::Tensor attention_prefill_v2(torch::Tensor q, torch::Tensor k,
-                                   torch::Tensor v, bool causal, double scale,
-                                   c10::optional<torch::Tensor> seq_lens,
-                                   bool bshd, bool kdirect, bool pipe);
-torch::Tensor attention_prefill_paged_v2(
-    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
-    torch::Tensor block_table, torch::Tensor kv_lens, torch::Tensor q_lens,
-    double scale, c10::optional<torch::Tensor> k_scale,
-    c10::optional<torch::Tensor> v_scale);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "clearml-serving-amd gfx950 kernel library";
@@ -86,7 +77,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_bf16", &gemm_bf16);
   m.def("skinny_gemm", &skinny_gemm, py::arg("a"), py::arg("w"),
         py::arg("variant") = 0);
-  m.def("attention_prefill_paged", &attention_prefill_paged);
+  m.def("attention_prefill_paged", &attention_prefill_paged, py::arg("q"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
+        py::arg("kv_lens"), py::arg("q_lens"), py::arg("scale"),
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("rmsnorm_fp8", &rmsnorm_fp8, py::arg("x"), py::arg("weight"),
         py::arg("eps") = 1e-6, py::arg("residual") = py::none());
   m.def("silu_mul_fp8", &silu_mul_fp8);
@@ -96,13 +90,4 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3_nhwc", &conv3x3_nhwc, py::arg("x"), py::arg("w"),
         py::arg("bias") = py::none(), py::arg("relu") = false,
         py::arg("residual") = py::none());
-  m.def("attention_prefill_v2", &attention_prefill_v2, py::arg("q"),
-        py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("scale"),
-        py::arg("seq_lens") = py::none(), py::arg("bshd") = false,
-        py::arg("kdirect") = false, py::arg("pipe") = false);
-  m.def("attention_prefill_paged_v2", &attention_prefill_paged_v2,
-        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
-        py::arg("block_table"), py::arg("kv_lens"), py::arg("q_lens"),
-        py::arg("scale"), py::arg("k_scale") = py::none(),
-        py::arg("v_scale") = py::none());
 }

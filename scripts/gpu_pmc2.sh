@@ -20,12 +20,12 @@ wt = (torch.randn(128, 128, 3, 3, device="cuda") / 8).to(torch.bfloat16) \
 for _ in range(20):
     ext.conv3x3_nhwc(x, wt, None, True, None)
 
-# attention v2, llama-8b s2048 causal
+# attention prefill, llama-8b s2048 causal
 q = (torch.randn(4, 32, 2048, 128, device="cuda") / 4).to(torch.bfloat16)
 k = (torch.randn(4, 8, 2048, 128, device="cuda") / 4).to(torch.bfloat16)
 v = (torch.randn(4, 8, 2048, 128, device="cuda") / 4).to(torch.bfloat16)
 for _ in range(10):
-    ext.attention_prefill_v2(q, k, v, True, 128 ** -0.5, None, False)
+    ext.attention_prefill(q, k, v, True, 128 ** -0.5, None, False)
 
 # skinny fp8, qkv M=1
 a = (torch.randn(1, 4096, device="cuda") / 8).to(torch.bfloat16)
@@ -52,7 +52,7 @@ for f in files:
         name = r["Kernel_Name"]
         key = None
         if "conv3x3" in name: key = "conv3x3"
-        elif "attn_prefill_v2" in name: key = "attn_v2"
+        elif "attn_prefill_kernel" in name: key = "attn"
         elif "skinny_gemm_fp8" in name: key = "skinny_fp8"
         if key:
             agg[key][r["Counter_Name"]] += float(r["Counter_Value"])

@@ -290,7 +290,7 @@ def test_decode_graphs_match_eager():
 
 # --------------------------------------------------------------------- #
 # fp8 KV cache (attention_decode.hip FP8KV / kv_cache_write_fp8_kernel /
-# attention_v2.hip FP8KV paged prefill)
+# attention.hip FP8KV paged prefill)
 # --------------------------------------------------------------------- #
 def test_kv_cache_write_fp8_matches_cpu_quantizer():
     torch.manual_seed(4)

@@ -26,7 +26,7 @@ DEV = "cuda:0"
 
 def test_spec_decode_gpu_matches_plain_greedy():
     """ngram speculative decoding on the GPU kernel path (multi-token
-    verify through attention_prefill_paged_v2): token-identical to plain
+    verify through attention_prefill_paged): token-identical to plain
     greedy decode, and speculation actually fires."""
     def gen(speculative):
         torch.manual_seed(11)
