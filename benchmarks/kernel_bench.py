@@ -121,17 +121,59 @@ def bench_sampling(results):
                         gbps=logits.numel() * 2 / dt / 1e9))
 
 
+def bench_lora(results):
+    """Multi-LoRA decode step: shrink + expand (csrc/lora.hip) at T=64 rows
+    over L=4 adapters of rank 16, for the four merged llama-3-8b
+    projections, next to the eager torch composition of the same math
+    (index_select + bmm + add)."""
+    t, nl, r = 64, 4, 16
+    h, q_out, kv_out, inter = 4096, 4096, 1024, 14336
+    idx = (torch.arange(t, device="cuda") % nl).to(torch.int32)
+    sel = idx.long()
+    for name, k, n, parts in [("qkv", h, q_out + 2 * kv_out, 3),
+                              ("o_proj", q_out, h, 1),
+                              ("gate_up", h, 2 * inter, 2),
+                              ("down", inter, h, 1)]:
+        rr = parts * r  # A matrices of a merged projection stack along rank
+        x = torch.randn(t, k, device="cuda", dtype=torch.bfloat16)
+        a = torch.randn(nl, rr, k, device="cuda", dtype=torch.bfloat16) \
+            * k ** -0.5
+        b = torch.randn(nl, n, rr, device="cuda", dtype=torch.bfloat16)
+        out = torch.zeros(t, n, device="cuda", dtype=torch.bfloat16)
+
+        def ours():
+            ops.lora_expand_add(ops.lora_shrink(x, a, idx), b, idx, out)
+
+        def eager():
+            y = torch.bmm(a.index_select(0, sel), x.unsqueeze(-1))
+            out.add_(torch.bmm(b.index_select(0, sel), y).squeeze(-1))
+
+        # per-token A and B rows + x read + out read/write
+        bytes_moved = 2.0 * t * (rr * k + n * rr + k + 2 * n)
+        shape = "{}:t{}k{}n{}r{}".format(name, t, k, n, rr)
+        for op, fn in (("lora_shrink_expand", ours),
+                       ("lora_eager_bmm", eager)):
+            dt = timeit(fn)
+            results.append(dict(op=op, shape=shape, us=dt * 1e6,
+                                gbps=bytes_moved / dt / 1e9))
+
+
+BENCHES = {"attention": bench_attention, "decode": bench_decode,
+           "memops": bench_memops, "gemm": bench_gemm,
+           "sampling": bench_sampling, "lora": bench_lora}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--only", type=str, default=None, choices=sorted(BENCHES),
+                    help="run one entry instead of all")
     args = ap.parse_args()
     assert torch.cuda.is_available() and ops.has_extension()
     results = []
-    bench_attention(results)
-    bench_decode(results)
-    bench_memops(results)
-    bench_gemm(results)
-    bench_sampling(results)
+    for name, fn in BENCHES.items():
+        if args.only in (None, name):
+            fn(results)
     for r in results:
         perf = ("{:8.1f} TF".format(r["tflops"]) if "tflops" in r
                 else "{:8.1f} GB/s".format(r["gbps"]))

@@ -271,6 +271,12 @@ class LlmEngineConfig:
                                 # batch bucket (GPU, TP=1): collapses the
                                 # ~350 Python-dispatched launches of a
                                 # llama-8B decode step into one replay
+    # multi-LoRA serving (vLLM parity): [{"name": ..., "path": ...}] PEFT
+    # adapter directories served on this one base model; a request picks
+    # one through the OpenAI "model" field. Relative paths resolve against
+    # the model directory. llama family, bf16/fp32 weights, TP=1.
+    lora_modules: Optional[List[Dict[str, str]]] = None
+    max_lora_rank: int = 16
 
     @classmethod
     def from_aux(cls, model_path: Optional[str], aux: Dict[str, Any]):
@@ -297,12 +303,20 @@ class LlmEngineConfig:
                     "max_model_len", "max_prefill_tokens", "prefill_chunk",
                     "gpu_memory_fraction", "num_kv_blocks", "quantization",
                     "kv_dtype", "weights", "device", "decode_graphs",
-                    "speculative", "enable_prefix_caching"):
+                    "speculative", "enable_prefix_caching", "lora_modules",
+                    "max_lora_rank"):
             for src in (card, aux):
                 if key in src and src[key] is not None:
                     setattr(cfg, key, src[key])
         cfg.overrides = {**card.get("overrides", {}),
                          **(aux.get("overrides") or {})}
+        if cfg.lora_modules:
+            base_dir = (model_path if model_path and os.path.isdir(model_path)
+                        else os.path.dirname(model_path or ""))
+            cfg.lora_modules = [
+                {**m, "path": os.path.join(base_dir, str(m.get("path", "")))}
+                if isinstance(m, dict) else m  # start() rejects non-dicts
+                for m in cfg.lora_modules]
         return cfg
 
 
@@ -355,21 +369,24 @@ class PrefixCacheAllocator(BlockAllocator):
         self.hits = 0        # cached blocks reused
         self.hit_tokens = 0  # prompt tokens skipped
 
-    def _chain_hashes(self, prompt_ids: List[int]) -> List[int]:
+    def _chain_hashes(self, prompt_ids: List[int],
+                      salt: int = 0) -> List[int]:
+        # ``salt`` seeds the chain: K/V depends on the LoRA adapter, so each
+        # adapter hashes into its own block namespace (0 = base model)
         bs = self.block_size
         out = []
-        h = 0
+        h = salt
         for i in range(len(prompt_ids) // bs):
             h = hash((h, tuple(prompt_ids[i * bs:(i + 1) * bs])))
             out.append(h)
         return out
 
-    def match(self, prompt_ids: List[int]):
+    def match(self, prompt_ids: List[int], salt: int = 0):
         """Longest cached chain for this prompt -> (block_ids, n_tokens,
         chain_hash at the match point); matched blocks are ref'd
         (protected from eviction) immediately."""
         blocks: List[int] = []
-        hashes = self._chain_hashes(prompt_ids)
+        hashes = self._chain_hashes(prompt_ids, salt)
         for h in hashes:
             b = self._hash2block.get(h)
             if b is None:
@@ -386,7 +403,7 @@ class PrefixCacheAllocator(BlockAllocator):
             meta[1] += 1
         # hit stats are recorded by the caller on successful admission
         # (a match may be released when the admission budget refuses it)
-        chain = hashes[len(blocks) - 1] if blocks else 0
+        chain = hashes[len(blocks) - 1] if blocks else salt
         return blocks, len(blocks) * self.block_size, chain
 
     def register_block(self, prev_hash: int, tokens: List[int],
@@ -432,8 +449,13 @@ class PrefixCacheAllocator(BlockAllocator):
 
 class Sequence:
     def __init__(self, req_id: str, prompt_ids: List[int],
-                 params: SamplingParams):
+                 params: SamplingParams, lora_idx: int = -1,
+                 cache_salt: int = 0):
         self.req_id = req_id
+        # LoRA adapter slot in the engine's bank (-1 = base model) and the
+        # prefix-cache chain seed that goes with it; both survive preemption
+        self.lora_idx = lora_idx
+        self.cache_salt = cache_salt
         self.prompt_ids = prompt_ids
         self.output_ids: List[int] = []
         self.generated = 0  # survives preemption (output folds into prompt)
@@ -502,7 +524,11 @@ class LlmEngine:
                       "prefill_batches": 0, "decode_batches": 0,
                       "preemptions": 0, "aborts": 0,
                       "graph_captures": 0, "graph_replays": 0,
-                      "spec_proposed": 0, "spec_accepted": 0}
+                      "spec_proposed": 0, "spec_accepted": 0,
+                      "lora_requests": 0}
+        # multi-LoRA: models.lora.LoraBank built by start() when
+        # cfg.lora_modules is set; None = every path below runs as before
+        self.lora_bank = None
 
     # ------------------------------------------------------------------ #
     def start(self) -> None:
@@ -518,6 +544,8 @@ class LlmEngine:
         torch.manual_seed(1234)  # identical replicated params across ranks
         gpt2 = (str(cfg.arch).lower() == "gpt2"
                 or str(cfg.preset).startswith("gpt2"))
+        lora_adapters = (self._load_lora_adapters(gpt2)
+                         if cfg.lora_modules else None)
         if gpt2:
             # GPT-2 family: same engine-facing forward interface as llama
             # (paged kv_caches + attn_ctx modes), so scheduling, chunked
@@ -576,6 +604,13 @@ class LlmEngine:
                     "fp8 quantization covers the llama-family projections "
                     "only (arch '{}' has none)".format(cfg.arch))
             print("[llm] fp8-quantized {} projection layers".format(n))
+        if lora_adapters:
+            from ...models.lora import LoraBank
+
+            self.lora_bank = LoraBank(lora_adapters, mcfg, cfg.max_lora_rank,
+                                      self.device, self.dtype)
+            print("[llm] serving {} LoRA adapters: {}".format(
+                len(self.lora_bank), ", ".join(self.lora_bank.names)))
 
         self.tokenizer = (HfTokenizer(cfg.tokenizer_path)
                           if cfg.tokenizer_path else SimpleTokenizer())
@@ -638,10 +673,65 @@ class LlmEngine:
         self._started = True
 
     # ------------------------------------------------------------------ #
+    # multi-LoRA (models/lora.py; kernels ops/csrc/lora.hip)
+    # ------------------------------------------------------------------ #
+    def _load_lora_adapters(self, gpt2: bool) -> List:
+        """Validate cfg.lora_modules and read the adapters (cheap: before
+        the base model is built). Combinations this engine does not serve
+        raise instead of silently ignoring the adapters."""
+        from ...models.lora import load_adapter
+
+        cfg = self.cfg
+        if gpt2:
+            raise ValueError("lora_modules serve the llama family only "
+                             "(arch=gpt2 has no adapter hook)")
+        if cfg.quantization == "fp8":
+            raise ValueError(
+                "lora_modules are not supported with quantization='fp8': "
+                "the fp8 path never materialises the bf16 activation the "
+                "adapter reads")
+        if self.tp_size > 1:
+            raise ValueError("lora_modules are not supported under tensor "
+                             "parallelism (tp_size={})".format(self.tp_size))
+        adapters = []
+        for m in cfg.lora_modules:
+            if not isinstance(m, dict) or not m.get("name") \
+                    or not m.get("path"):
+                raise ValueError(
+                    "lora_modules entries must be {{'name': ..., 'path': "
+                    "...}}, got {!r}".format(m))
+            adapters.append(load_adapter(str(m["path"]),
+                                         int(cfg.max_lora_rank),
+                                         name=str(m["name"])))
+        return adapters
+
+    def _resolve_lora(self, model: Any) -> int:
+        """OpenAI ``model`` field -> adapter slot; anything that is not a
+        configured adapter name serves the base model (-1)."""
+        if self.lora_bank is None or not isinstance(model, str):
+            return -1
+        return self.lora_bank.index.get(model, -1)
+
+    def _lora_ctx(self, attn_ctx: Dict[str, Any], rows: List[int],
+                  lens: Optional[List[int]] = None,
+                  smax: int = 1) -> None:
+        """Expand per-sequence adapter slots to the per-token int32 idx the
+        kernels take and attach it to attn_ctx; padded tokens get -1."""
+        if lens is None:
+            idx = torch.tensor(rows, dtype=torch.int32)
+        else:
+            idx = torch.full((len(rows), smax), -1, dtype=torch.int32)
+            for i, n in enumerate(lens):
+                idx[i, :n] = rows[i]
+            idx = idx.view(-1)
+        attn_ctx["lora"] = (self.lora_bank, idx.to(self.device))
+
+    # ------------------------------------------------------------------ #
     # request API
     # ------------------------------------------------------------------ #
     async def add_request(self, prompt_ids: List[int],
-                          params: SamplingParams) -> Sequence:
+                          params: SamplingParams,
+                          lora_idx: int = -1) -> Sequence:
         if self._stopped:
             raise RuntimeError("LLM engine stopped (endpoint was removed)")
         if len(prompt_ids) >= self.cfg.max_model_len:
@@ -661,7 +751,15 @@ class LlmEngine:
         if params.min_tokens > 0 and getattr(self, "tp_size", 1) > 1:
             raise ValueError(
                 "min_tokens is not supported under tensor parallelism yet")
-        seq = Sequence(uuid.uuid4().hex, prompt_ids, params)
+        if lora_idx >= 0:
+            if self.lora_bank is None or lora_idx >= len(self.lora_bank):
+                raise ValueError("no LoRA adapter in slot {}".format(lora_idx))
+            seq = Sequence(uuid.uuid4().hex, prompt_ids, params,
+                           lora_idx=lora_idx,
+                           cache_salt=self.lora_bank.salts[lora_idx])
+            self.stats["lora_requests"] += 1
+        else:
+            seq = Sequence(uuid.uuid4().hex, prompt_ids, params)
         self.waiting.append(seq)
         self._ensure_loop()
         self._wake.set()
@@ -683,10 +781,11 @@ class LlmEngine:
         if self._wake is not None:
             self._wake.set()  # free the pages promptly even when idle
 
-    async def generate(self, prompt: str, params: SamplingParams
+    async def generate(self, prompt: str, params: SamplingParams,
+                       lora_idx: int = -1
                        ) -> AsyncGenerator[Dict[str, Any], None]:
         ids = self.tokenizer.encode(prompt)
-        seq = await self.add_request(ids, params)
+        seq = await self.add_request(ids, params, lora_idx)
         try:
             while True:
                 item = await seq.stream.get()
@@ -699,12 +798,14 @@ class LlmEngine:
                 self.abort(seq)
 
     async def generate_simple(self, body: Dict[str, Any]) -> Dict[str, Any]:
-        """Non-OpenAI route: {"prompt": str, "max_tokens": ...}."""
+        """Non-OpenAI route: {"prompt": str, "max_tokens": ...}; an
+        optional "lora" key names a configured adapter."""
         prompt = body.get("prompt") or body.get("text") or ""
         params = SamplingParams.from_request(body)
         tokens: List[int] = []
         reason = None
-        async for item in self.generate(prompt, params):
+        async for item in self.generate(prompt, params,
+                                        self._resolve_lora(body.get("lora"))):
             if item.get("error"):
                 raise RuntimeError("generation failed: {}".format(
                     item["error"]))
@@ -866,7 +967,7 @@ class LlmEngine:
             chain = 0
             if prefix_cache:
                 cached, ncached, chain = self.allocator.match(
-                    seq.prompt_ids)
+                    seq.prompt_ids, seq.cache_salt)
             need = len(seq.prompt_ids) - ncached
             if admitted and tokens + need > self.cfg.max_prefill_tokens:
                 if cached:
@@ -943,6 +1044,8 @@ class LlmEngine:
                       for s in seqs],
             "sample": self._sample_spec(seqs),
         }
+        if self.lora_bank is not None:
+            plan["lora"] = [s.lora_idx for s in seqs]
         self._tp_broadcast(plan)
         logits = self._exec_prefill(plan)
         self.stats["prompt_tokens"] += sum(len(p) for p in plan["prompts"])
@@ -1005,6 +1108,8 @@ class LlmEngine:
         done_seqs = [s for (s, c), comp in zip(batch, plan["complete"])
                      if comp]
         plan["sample"] = self._sample_spec(done_seqs)
+        if self.lora_bank is not None:
+            plan["lora"] = [s.lora_idx for s, c in batch]
         self._tp_broadcast(plan)
         logits = self._exec_chunk(plan)
         done = []
@@ -1045,6 +1150,8 @@ class LlmEngine:
             "block_table": btab.to(dev),
             "slot_mapping": slot_map.view(-1).to(dev),
         }
+        if "lora" in plan:
+            self._lora_ctx(attn_ctx, plan["lora"], lens, smax)
         rows = [i * smax + lens[i] - 1
                 for i in range(b) if plan["complete"][i]]
         last_idx = torch.tensor(rows, dtype=torch.long, device=dev)
@@ -1076,6 +1183,8 @@ class LlmEngine:
             "seq_lens": seq_lens,
             "slot_mapping": slot_map.view(-1).to(dev),
         }
+        if "lora" in plan:
+            self._lora_ctx(attn_ctx, plan["lora"], lens, smax)
         last_idx = torch.tensor(
             [i * smax + lens[i] - 1 for i in range(b)], dtype=torch.long,
             device=dev)
@@ -1186,6 +1295,8 @@ class LlmEngine:
             "blocks": [list(s.blocks) for s in seqs],
             "sample": self._sample_spec(seqs),
         }
+        if self.lora_bank is not None:
+            plan["lora"] = [s.lora_idx for s in seqs]
         self._tp_broadcast(plan)
         logits = self._exec_decode(plan)
         self._sample_and_emit(seqs, logits, sample=plan["sample"])
@@ -1224,6 +1335,8 @@ class LlmEngine:
             "block_table": btab.to(dev),
             "slot_mapping": slot_map,
         }
+        if "lora" in plan:
+            self._lora_ctx(attn_ctx, plan["lora"])
         return self.model(tokens, positions, kv_caches=self.kv_caches,
                           attn_ctx=attn_ctx, last_token_idx=None,
                           gather_logits=False)
@@ -1361,6 +1474,8 @@ class LlmEngine:
                       for s, prop in zip(seqs, proposals)],
             "blocks": [list(s.blocks) for s in seqs],
         }
+        if self.lora_bank is not None:
+            plan["lora"] = [s.lora_idx for s in seqs]
         logits = self._exec_spec(plan)
 
         off = 0
@@ -1414,6 +1529,8 @@ class LlmEngine:
             "block_table": btab.to(dev),
             "slot_mapping": slot_map.view(-1).to(dev),
         }
+        if "lora" in plan:
+            self._lora_ctx(attn_ctx, plan["lora"], lens, smax)
         rows = [i * smax + j for i in range(b) for j in range(lens[i])]
         last_idx = torch.tensor(rows, dtype=torch.long, device=dev)
         return self.model(tokens.view(-1).to(dev),
@@ -1463,6 +1580,12 @@ class LlmEngine:
         attn_ctx = {"mode": "decode", "seq_lens": static["seq_lens"],
                     "block_table": static["block_table"],
                     "slot_mapping": static["slots"]}
+        if self.lora_bank is not None:
+            # one graph per bucket whatever the adapter mix: the captured
+            # LoRA kernels read this buffer; padded rows stay -1 (skipped)
+            static["lora_idx"] = torch.full((bucket,), -1, dtype=torch.int32,
+                                            device=dev)
+            attn_ctx["lora"] = (self.lora_bank, static["lora_idx"])
 
         def fwd():
             return self.model(static["tokens"], static["positions"],
@@ -1528,6 +1651,14 @@ class LlmEngine:
             bt[i, :len(bl)] = torch.tensor(bl, dtype=torch.int32)
         for k in ("tokens", "positions", "slots", "seq_lens", "block_table"):
             entry[k].copy_(pin[k], non_blocking=True)
+        if "lora" in plan:
+            if "lora_idx" not in pin:
+                pin["lora_idx"] = torch.empty(bucket, dtype=torch.int32,
+                                              pin_memory=True)
+            pin["lora_idx"][:b] = torch.tensor(plan["lora"],
+                                               dtype=torch.int32)
+            pin["lora_idx"][b:] = -1  # padded rows: LoRA kernels skip idx<0
+            entry["lora_idx"].copy_(pin["lora_idx"], non_blocking=True)
         entry["graph"].replay()
         self.stats["graph_replays"] += 1
         return entry["logits"][:b]
@@ -1867,14 +1998,20 @@ class LlmEngine:
         n = self._n_choices(body)
         params = self._choice_params(body, n)
         rid = "chatcmpl-" + uuid.uuid4().hex[:24]
+        # "model" naming a configured LoRA adapter routes to it (and is
+        # echoed); any other value serves the base model
+        lora_idx = self._resolve_lora(body.get("model"))
+        if lora_idx >= 0:
+            model_name = body["model"]
         if body.get("stream"):
             opts = body.get("stream_options") or {}
             return self._sse_stream(prompt, params[0], rid, model_name,
                                     chat=True,
                                     include_usage=bool(
-                                        opts.get("include_usage")))
+                                        opts.get("include_usage")),
+                                    lora_idx=lora_idx)
         results = await asyncio.gather(
-            *[self._collect(prompt, p) for p in params])
+            *[self._collect(prompt, p, lora_idx) for p in params])
         nprompt = results[0][3]
         ntok = sum(r[2] for r in results)
         choices = []
@@ -1905,14 +2042,18 @@ class LlmEngine:
         n = self._n_choices(body)
         params = self._choice_params(body, n)
         rid = "cmpl-" + uuid.uuid4().hex[:24]
+        lora_idx = self._resolve_lora(body.get("model"))
+        if lora_idx >= 0:
+            model_name = body["model"]
         if body.get("stream"):
             opts = body.get("stream_options") or {}
             return self._sse_stream(prompt, params[0], rid, model_name,
                                     chat=False,
                                     include_usage=bool(
-                                        opts.get("include_usage")))
+                                        opts.get("include_usage")),
+                                    lora_idx=lora_idx)
         results = await asyncio.gather(
-            *[self._collect(prompt, p) for p in params])
+            *[self._collect(prompt, p, lora_idx) for p in params])
         nprompt = results[0][3]
         ntok = sum(r[2] for r in results)
         echo = bool(body.get("echo"))
@@ -1921,7 +2062,8 @@ class LlmEngine:
             ids = self.tokenizer.encode(prompt)
             if len(ids) > 1:
                 prompt_lps = await asyncio.to_thread(
-                    self._prompt_logprobs_sync, ids, params[0].logprobs)
+                    self._prompt_logprobs_sync, ids, params[0].logprobs,
+                    lora_idx)
             if ids:
                 # the first prompt token has no predecessor: null logprob
                 prompt_lps = [{"token_ids": [ids[0]], "logprob": None,
@@ -1944,9 +2086,17 @@ class LlmEngine:
         }
 
     def openai_models(self, model_name: str):
-        return {"object": "list",
-                "data": [{"id": model_name, "object": "model",
-                          "owned_by": "clearml-serving-amd"}]}
+        data = [{"id": model_name, "object": "model",
+                 "owned_by": "clearml-serving-amd"}]
+        if self.lora_bank is not None:
+            # adapters are addressable ids of their own (vLLM's layout:
+            # parent = the base model, root = where the adapter came from)
+            for name, path in zip(self.lora_bank.names,
+                                  self.lora_bank.paths):
+                data.append({"id": name, "object": "model",
+                             "owned_by": "clearml-serving-amd",
+                             "parent": model_name, "root": path})
+        return {"object": "list", "data": data}
 
     async def openai_embeddings(self, body: Dict[str, Any], model_name: str):
         inp = body.get("input")
@@ -2020,12 +2170,13 @@ class LlmEngine:
     def openai_detokenize(self, body: Dict[str, Any]):
         return {"prompt": self.tokenizer.decode(body.get("tokens") or [])}
 
-    async def _collect(self, prompt: str, params: SamplingParams):
+    async def _collect(self, prompt: str, params: SamplingParams,
+                       lora_idx: int = -1):
         ids = self.tokenizer.encode(prompt)
         tokens: List[int] = []
         reason = None
         lps: List[dict] = []
-        async for item in self.generate(prompt, params):
+        async for item in self.generate(prompt, params, lora_idx):
             if item.get("error"):
                 # engine-side failure: surface it (the route maps to 500)
                 # instead of returning truncated text as if successful
@@ -2041,7 +2192,8 @@ class LlmEngine:
             self.tokenizer.decode(tokens), params, reason)
         return text, reason, len(tokens), len(ids), lps
 
-    def _prompt_logprobs_sync(self, ids: List[int], k: int) -> List[dict]:
+    def _prompt_logprobs_sync(self, ids: List[int], k: int,
+                              lora_idx: int = -1) -> List[dict]:
         """Teacher-forced logprobs of the prompt tokens themselves (the
         completions echo+logprobs contract): row i-1's distribution scores
         token i; the first token has no predecessor (None upstream).
@@ -2059,6 +2211,8 @@ class LlmEngine:
                     "slot_mapping": torch.full((n,), -1, dtype=torch.int32,
                                                device=dev),
                 }
+                if lora_idx >= 0:
+                    self._lora_ctx(attn_ctx, [lora_idx] * n)
                 logits = self.model(tokens, positions, kv_caches=None,
                                     attn_ctx=attn_ctx)
                 lsm = torch.log_softmax(logits.float(), dim=-1)
@@ -2114,12 +2268,12 @@ class LlmEngine:
 
     def _sse_stream(self, prompt: str, params: SamplingParams, rid: str,
                     model_name: str, chat: bool,
-                    include_usage: bool = False):
+                    include_usage: bool = False, lora_idx: int = -1):
         from fastapi.responses import StreamingResponse
 
         async def gen():
             ntok = 0
-            async for item in self.generate(prompt, params):
+            async for item in self.generate(prompt, params, lora_idx):
                 ntok += len(item.get("token_ids", []))
                 if item.get("error"):
                     yield "data: {}\n\n".format(json.dumps(

@@ -47,9 +47,11 @@ class LlamaConfig:
 
 
 class LlamaLayer(nn.Module):
-    def __init__(self, cfg: LlamaConfig, tp_rank: int = 0, tp_size: int = 1):
+    def __init__(self, cfg: LlamaConfig, tp_rank: int = 0, tp_size: int = 1,
+                 layer_idx: int = 0):
         super().__init__()
         self.cfg = cfg
+        self.layer_idx = layer_idx  # this layer's slice of a LoraBank
         assert cfg.heads % tp_size == 0 and cfg.kv_heads % tp_size == 0, \
             "TP degree must divide head counts"
         self.heads = cfg.heads // tp_size
@@ -80,13 +82,21 @@ class LlamaLayer(nn.Module):
             return y
         return mod(x)
 
+    def _lora(self, proj, x, out, lora):
+        """Add the per-token adapter delta to a projection output in place
+        (multi-LoRA serving, models/lora.py): lora = (bank, idx int32 [T]),
+        rows with idx -1 keep the base output bit-identical."""
+        bank, idx = lora
+        a, b = bank.layer(self.layer_idx, proj)
+        ops.lora_expand_add(ops.lora_shrink(x, a, idx), b, idx, out)
+
     def forward(self, x, residual, positions, kv_cache, attn_ctx):
         attn_out = self.attn_half(x, residual, positions, kv_cache, attn_ctx)
         if self.tp_size > 1:
             from ..parallel import tp as tp_mod
 
             tp_mod.maybe_all_reduce(attn_out)  # row-parallel o_proj
-        mlp_out = self.mlp_half(attn_out, residual)
+        mlp_out = self.mlp_half(attn_out, residual, attn_ctx.get("lora"))
         if self.tp_size > 1:
             from ..parallel import tp as tp_mod
 
@@ -99,6 +109,8 @@ class LlamaLayer(nn.Module):
         (LlamaForCausalLM.forward_pipelined) issues that reduce async so it
         overlaps the other microbatch's compute."""
         cfg = self.cfg
+        # optional (LoraBank, idx [T]) entry: absent -> the base path below
+        lora = attn_ctx.get("lora")
         # fp8 serving path (models/quant.py): activation quantization is
         # FUSED into the producing kernels -- rmsnorm/silu_mul emit fp8
         # bytes + per-row scales in the same HBM pass
@@ -113,6 +125,8 @@ class LlamaLayer(nn.Module):
             x = ops.rmsnorm(x, self.attn_norm, cfg.rms_eps, residual=residual)
             t = x.shape[0]
             qkv = self._proj(self.qkv, x)
+            if lora is not None:  # after the Qwen2 bias add in _proj
+                self._lora("qkv", x, qkv, lora)
         # token-strided views into the merged projection -- the rope /
         # kv_cache_write / decode-attention kernels are stride-aware, so no
         # .contiguous() copies on the decode hot path
@@ -163,11 +177,13 @@ class LlamaLayer(nn.Module):
             attn_out = self.o_proj.forward_q(c8, cs)
         else:
             attn_out = self._proj(self.o_proj, ctx)
+            if lora is not None:
+                self._lora("o_proj", ctx, attn_out, lora)
         return attn_out
 
-    def mlp_half(self, attn_out, residual):
+    def mlp_half(self, attn_out, residual, lora=None):
         """norm -> gate_up -> silu*up -> down, WITHOUT the row-parallel
-        all-reduce (see attn_half)."""
+        all-reduce (see attn_half). ``lora``: attn_ctx["lora"] or None."""
         cfg = self.cfg
         fp8 = not isinstance(self.qkv, nn.Linear)
         if fp8:
@@ -181,8 +197,13 @@ class LlamaLayer(nn.Module):
             x = ops.rmsnorm(attn_out, self.mlp_norm, cfg.rms_eps,
                             residual=residual)
             gate_up = self.gate_up(x)
+            if lora is not None:
+                self._lora("gate_up", x, gate_up, lora)
             gate, up = gate_up.split([self.inter, self.inter], dim=-1)
-            mlp_out = self._proj(self.down, ops.silu_mul(gate, up))
+            act = ops.silu_mul(gate, up)
+            mlp_out = self._proj(self.down, act)
+            if lora is not None:
+                self._lora("down", act, mlp_out, lora)
         return mlp_out
 
 
@@ -193,7 +214,8 @@ class LlamaForCausalLM(nn.Module):
         self.tp_rank, self.tp_size = tp_rank, tp_size
         self.embed = nn.Embedding(cfg.vocab_size, cfg.hidden)
         self.layers = nn.ModuleList(
-            [LlamaLayer(cfg, tp_rank, tp_size) for _ in range(cfg.layers)])
+            [LlamaLayer(cfg, tp_rank, tp_size, layer_idx=i)
+             for i in range(cfg.layers)])
         self.final_norm = nn.Parameter(torch.ones(cfg.hidden))
         # TP: lm_head column-parallel over vocab (shards all-gathered)
         assert cfg.vocab_size % tp_size == 0

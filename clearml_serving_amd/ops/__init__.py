@@ -620,3 +620,46 @@ def skinny_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
             if ext is not None:
                 return ext.skinny_gemm(x.contiguous(), weight, 1)
     return torch.nn.functional.linear(x, weight)
+
+
+# --------------------------------------------------------------------- #
+# Multi-LoRA (BGMV-style): per-token adapter deltas in one launch each
+# (kernels: csrc/lora.hip)
+# --------------------------------------------------------------------- #
+def lora_shrink(x: torch.Tensor, a: torch.Tensor,
+                idx: torch.Tensor) -> torch.Tensor:
+    """y[t] = A[idx[t]] @ x[t] -> fp32 [T, R].
+
+    x: [T, K]; a: [L, R, K] stacked adapter A matrices; idx: int32 [T] in
+    [-1, L) (PRECONDITION: idx < L is not checked on the GPU path -- that
+    would cost a device sync). Rows with idx == -1 (base model, decode-graph
+    padding) are skipped: the GPU kernel leaves them unwritten, the
+    reference zeroes them. GPU: bf16, K % 8 == 0, R % 16 == 0, R <= 256."""
+    if x.is_cuda:
+        ext = _require_ext("lora_shrink")
+        if ext is not None:
+            return ext.lora_shrink(x.contiguous(), a, idx)
+    sel = a.float().index_select(0, idx.clamp(min=0).long())  # [T, R, K]
+    y = torch.bmm(sel, x.float().unsqueeze(-1)).squeeze(-1)
+    return torch.where((idx >= 0).unsqueeze(-1), y, torch.zeros_like(y))
+
+
+def lora_expand_add(y: torch.Tensor, b: torch.Tensor, idx: torch.Tensor,
+                    out: torch.Tensor) -> torch.Tensor:
+    """out[t] += B[idx[t]] @ y[t], in place (fp32 accumulation, one
+    rounding to out's dtype); returns ``out``.
+
+    y: fp32 [T, R] from lora_shrink; b: [L, N, R] with alpha/r folded in;
+    out: contiguous [T, N]. Rows with idx == -1 keep ``out`` bit-identical
+    and their ``y`` row is never read."""
+    if out.is_cuda:
+        ext = _require_ext("lora_expand_add")
+        if ext is not None:
+            ext.lora_expand_add(y, b, idx, out)
+            return out
+    live = (idx >= 0).unsqueeze(-1)
+    sel = b.float().index_select(0, idx.clamp(min=0).long())  # [T, N, R]
+    yf = torch.where(live, y.float(), torch.zeros_like(y, dtype=torch.float32))
+    delta = torch.bmm(sel, yf.unsqueeze(-1)).squeeze(-1)
+    out.copy_(torch.where(live, (out.float() + delta).to(out.dtype), out))
+    return out

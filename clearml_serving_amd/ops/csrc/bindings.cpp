@@ -49,6 +49,9 @@ torch::Tensor skinny_gemm_fp8_v2(torch::Tensor a8, torch::Tensor a_scale,
 torch::Tensor conv3x3_nhwc(torch::Tensor x, torch::Tensor w,
                            c10::optional<torch::Tensor> bias, bool relu,
                            c10::optional<torch::Tensor> residual);
+torch::Tensor lora_shrink(torch::Tensor x, torch::Tensor a, torch::Tensor idx);
+void lora_expand_add(torch::Tensor y, torch::Tensor b, torch::Tensor idx,
+                     torch::Tensor out);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "clearml-serving-amd gfx950 kernel library";
@@ -90,4 +93,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3_nhwc", &conv3x3_nhwc, py::arg("x"), py::arg("w"),
         py::arg("bias") = py::none(), py::arg("relu") = false,
         py::arg("residual") = py::none());
+  m.def("lora_shrink", &lora_shrink, py::arg("x"), py::arg("a"),
+        py::arg("idx"));
+  m.def("lora_expand_add", &lora_expand_add, py::arg("y"), py::arg("b"),
+        py::arg("idx"), py::arg("out"));
 }

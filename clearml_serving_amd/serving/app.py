@@ -183,12 +183,30 @@ def create_app(
                 for url, ep in eps.items() if ep.engine_type in ("llm", "vllm")
             ]}
         out = await process_with_exceptions(
-            base_url=model, version=None,
+            base_url=_lora_base_endpoint(model), version=None,
             request_body=combined, serve_type=endpoint_type,
         )
         if isinstance(out, Response):
             return out
         return _jsonable(out)
+
+    def _lora_base_endpoint(model: str) -> str:
+        """Multi-LoRA: a ``model`` that is no endpoint but names an adapter
+        in an LLM endpoint's auxiliary ``lora_modules`` routes to that
+        endpoint; the body keeps the adapter name, which the engine
+        resolves to the adapter. Anything else passes through unchanged."""
+        proc = state["processor"]
+        eps = proc.get_synced_endpoints() if proc and model else {}
+        if model in eps:
+            return model
+        for url, ep in eps.items():
+            aux = ep.auxiliary_cfg if isinstance(ep.auxiliary_cfg, dict) \
+                else {}
+            if ep.engine_type in ("llm", "vllm") and any(
+                    isinstance(m, dict) and m.get("name") == model
+                    for m in aux.get("lora_modules") or []):
+                return url
+        return model
 
     @router.post("/{model_id}/{version}")
     @router.post("/{model_id}/")
