@@ -158,9 +158,57 @@ def bench_lora(results):
                                 gbps=bytes_moved / dt / 1e9))
 
 
+def bench_guided(results):
+    """Guided decoding sampling step (csrc/token_mask.hip), bf16 logits, a
+    density-0.5 bitmask bank: the out-of-place mask and the fused mask+draw
+    next to the eager torch composition of the same step (unpack bits ->
+    masked_fill -> argmax / the grouped gumbel sampler), same process."""
+    shifts = torch.arange(32, dtype=torch.int32, device="cuda")
+    for v in (32000, 128256):
+        words = (v + 31) // 32
+        bank = torch.randint(-2**31, 2**31 - 1, (64, words), device="cuda",
+                             dtype=torch.int32)
+        if v % 32:
+            bank[:, -1] &= (1 << (v % 32)) - 1
+        for b in (1, 8, 64):
+            logits = torch.randn(b, v, device="cuda", dtype=torch.bfloat16)
+            slot = (torch.arange(b, device="cuda") % 64).to(torch.int32)
+            greedy = torch.zeros(b, device="cuda")
+            temp = torch.full((b,), 0.8, device="cuda")
+            seed = torch.arange(b, device="cuda", dtype=torch.int32)
+
+            def eager_mask():
+                rows = bank.index_select(0, slot.long())
+                bits = ((rows.unsqueeze(-1) >> shifts) & 1).view(b, -1)
+                return logits.masked_fill(bits[:, :v] == 0, float("-inf"))
+
+            cases = [
+                ("guided_apply", lambda: ops.apply_token_bitmask(
+                    logits, bank, slot)),
+                ("guided_apply_eager", eager_mask),
+                ("guided_sample_greedy", lambda: ops.sample_token_bitmask(
+                    logits, bank, slot, greedy, seed)),
+                ("guided_greedy_eager", lambda: eager_mask().argmax(-1)),
+                ("guided_sample_fused", lambda: ops.sample_token_bitmask(
+                    logits, bank, slot, temp, seed)),
+                ("guided_apply+sampler", lambda: ops.sample_top_k_top_p(
+                    ops.apply_token_bitmask(logits, bank, slot),
+                    temperature=0.8)),
+                ("guided_sample_eager", lambda: ops.sample_top_k_top_p(
+                    eager_mask(), temperature=0.8)),
+            ]
+            # logits read (+ masked copy written by the apply variants)
+            for op, fn in cases:
+                dt = timeit(fn, iters=200, warmup=20)
+                results.append(dict(op=op, shape="{}x{}".format(b, v),
+                                    us=dt * 1e6,
+                                    gbps=logits.numel() * 2 / dt / 1e9))
+
+
 BENCHES = {"attention": bench_attention, "decode": bench_decode,
            "memops": bench_memops, "gemm": bench_gemm,
-           "sampling": bench_sampling, "lora": bench_lora}
+           "sampling": bench_sampling, "lora": bench_lora,
+           "guided": bench_guided}
 
 
 def main():

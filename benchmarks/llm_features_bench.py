@@ -36,10 +36,11 @@ def build(preset, **kw):
     return eng
 
 
-def run_prompts(eng, prompts, max_tokens):
+def run_prompts(eng, prompts, max_tokens, params=None):
     async def main():
-        params = SamplingParams(temperature=0.0, max_tokens=max_tokens,
-                                ignore_eos=True)
+        nonlocal params
+        params = params or SamplingParams(
+            temperature=0.0, max_tokens=max_tokens, ignore_eos=True)
 
         async def one(p):
             toks = []
@@ -67,6 +68,9 @@ def main():
     ap.add_argument("--preset", default="llama-tiny")
     ap.add_argument("--requests", type=int, default=16)
     ap.add_argument("--max-tokens", type=int, default=64)
+    ap.add_argument("--only", default=None,
+                    choices=["prefix", "spec", "guided"],
+                    help="run one section instead of all")
     args = ap.parse_args()
 
     shared = "You are a helpful assistant. Context: " + "lorem ipsum " * 40
@@ -76,7 +80,7 @@ def main():
     # issued in waves: blocks register when their prefill COMPUTES, so a
     # fully concurrent identical burst all misses (same first-arrival
     # semantics as vLLM); steady-state serving sees the reuse
-    for pc in (False, True):
+    for pc in ((False, True) if args.only in (None, "prefix") else ()):
         eng = build(args.preset, enable_prefix_caching=pc)
         dt = 0.0
         wave = max(len(prompts) // 3, 1)
@@ -98,8 +102,9 @@ def main():
 
     # ---- ngram speculation: decode forwards per token ---------------- #
     rep = "def add(a, b):\n    return a + b\n" * 6  # structured/repetitive
-    for spec in (None, {"method": "ngram", "num_spec_tokens": 4,
-                        "ngram": 2}):
+    for spec in ((None, {"method": "ngram", "num_spec_tokens": 4,
+                         "ngram": 2})
+                 if args.only in (None, "spec") else ()):
         eng = build(args.preset, speculative=spec)
         outs, dt = run_prompts(eng, [rep] * 4, args.max_tokens)
         gen = eng.stats["generated_tokens"]
@@ -112,6 +117,33 @@ def main():
             "proposed": eng.stats.get("spec_proposed", 0),
             "accepted": eng.stats.get("spec_accepted", 0),
             "wall_s": round(dt, 3)}), flush=True)
+        eng.stop()
+
+    # ---- guided decoding: decode out-tok/s, guided vs unguided -------- #
+    # every request emits exactly max_tokens tokens either way: the
+    # unguided run ignores eos, the guided one follows a regex of that
+    # length (sampled, so both take the per-row-temperature paths)
+    if args.only in (None, "guided"):
+        eng = build(args.preset, guided_decoding=True)
+        short = ["Q{}".format(i) for i in range(args.requests)]
+        regex = "[a-z ]{{{}}}".format(args.max_tokens)
+        for guided in (False, True, False, True):
+            params = (SamplingParams(temperature=0.8,
+                                     max_tokens=args.max_tokens + 8,
+                                     guided=("regex", regex))
+                      if guided else
+                      SamplingParams(temperature=0.8, ignore_eos=True,
+                                     max_tokens=args.max_tokens))
+            outs, dt = run_prompts(eng, short, args.max_tokens, params)
+            gen = sum(len(o) for o in outs)
+            print(json.dumps({
+                "bench": "guided_decoding", "guided": guided,
+                "preset": args.preset, "requests": args.requests,
+                "generated_tokens": gen,
+                "out_tok_per_s": round(gen / dt, 1),
+                "mask_hits": eng.stats["guided_mask_hits"],
+                "mask_misses": eng.stats["guided_mask_misses"],
+                "wall_s": round(dt, 3)}), flush=True)
         eng.stop()
 
 

@@ -119,13 +119,17 @@ class SamplingParams:
                                          # alongside each chosen token
     min_tokens: int = 0                  # ban eos/stop-token finishes until
                                          # this many tokens are generated
+    guided: Optional[tuple] = None       # (kind, spec) guided-decoding
+                                         # constraint (guided.py); engines
+                                         # with guided_decoding on only
 
     def has_penalties(self) -> bool:
         return bool(self.presence_penalty or self.frequency_penalty
                     or self.repetition_penalty != 1.0)
 
     @classmethod
-    def from_request(cls, body: Dict[str, Any], default_max: int = 128):
+    def from_request(cls, body: Dict[str, Any], default_max: int = 128,
+                     guided: bool = False):
         """Validate at add-request time so one malformed request 422s on its
         own instead of crashing the shared step() for every in-flight
         sequence (a bad temperature would assert inside the batched
@@ -198,9 +202,25 @@ class SamplingParams:
                 raise ValueError("'logprobs' must be an int or bool")
         if lp is not None and not (0 <= lp <= 20):
             raise ValueError("logprobs must be in [0, 20], got {}".format(lp))
+        constraint = None
+        if guided:
+            # the engine serves guided decoding: response_format json modes
+            # and the guided_* / structured_outputs fields become a grammar
+            from .guided import constraint_from_request
+
+            constraint = constraint_from_request(body)
+        else:
+            from .guided import GUIDED_FIELDS
+
+            for key in GUIDED_FIELDS:
+                if body.get(key) is not None:
+                    raise ValueError(
+                        "'{}' needs guided decoding, which this endpoint "
+                        "does not enable (set guided_decoding: true in the "
+                        "model card or aux config)".format(key))
         rf = body.get("response_format")
-        if rf and isinstance(rf, dict) and rf.get("type") not in (None,
-                                                                  "text"):
+        if not guided and rf and isinstance(rf, dict) \
+                and rf.get("type") not in (None, "text"):
             # grammar-constrained decoding (json_object/json_schema) is not
             # implemented; refuse instead of silently returning free text
             raise ValueError(
@@ -220,6 +240,14 @@ class SamplingParams:
             stop_ids = [int(t) for t in stop_ids]
         except (TypeError, ValueError, OverflowError):
             raise ValueError("'stop_token_ids' must be a list of ints")
+        ignore_eos = bool(body.get("ignore_eos", False))
+        if constraint is not None:
+            if ignore_eos:
+                raise ValueError("guided decoding cannot be combined with "
+                                 "ignore_eos (the grammar decides the end)")
+            if min_tokens > 0:
+                raise ValueError("guided decoding cannot be combined with "
+                                 "min_tokens > 0")
         return cls(
             temperature=temperature,
             top_k=top_k,
@@ -227,13 +255,14 @@ class SamplingParams:
             max_tokens=max_tokens,
             stop_token_ids=stop_ids,
             stop=[s for s in stop if s],
-            ignore_eos=bool(body.get("ignore_eos", False)),
+            ignore_eos=ignore_eos,
             seed=seed,
             presence_penalty=presence,
             frequency_penalty=frequency,
             repetition_penalty=repetition,
             logprobs=lp,
             min_tokens=min_tokens,
+            guided=constraint,
         )
 
 
@@ -277,6 +306,17 @@ class LlmEngineConfig:
     # the model directory. llama family, bf16/fp32 weights, TP=1.
     lora_modules: Optional[List[Dict[str, str]]] = None
     max_lora_rank: int = 16
+    # guided decoding (vLLM parity): response_format json_object /
+    # json_schema, guided_json / guided_regex / guided_choice and
+    # structured_outputs constrain the output to a grammar (guided.py);
+    # per-state token bitmasks live in a device bank of guided_mask_slots
+    # rows consumed by the token_mask kernels. Off by default. TP=1;
+    # byte-level BPE or the built-in byte tokenizer.
+    guided_decoding: bool = False
+    guided_mask_slots: int = 1024    # >= max_num_seqs
+    guided_max_states: int = 20000   # DFA size cap per constraint
+    guided_json_depth: int = 4       # container nesting bound of free-form
+                                     # JSON (json_object, untyped values)
 
     @classmethod
     def from_aux(cls, model_path: Optional[str], aux: Dict[str, Any]):
@@ -304,7 +344,8 @@ class LlmEngineConfig:
                     "gpu_memory_fraction", "num_kv_blocks", "quantization",
                     "kv_dtype", "weights", "device", "decode_graphs",
                     "speculative", "enable_prefix_caching", "lora_modules",
-                    "max_lora_rank"):
+                    "max_lora_rank", "guided_decoding", "guided_mask_slots",
+                    "guided_max_states", "guided_json_depth"):
             for src in (card, aux):
                 if key in src and src[key] is not None:
                     setattr(cfg, key, src[key])
@@ -473,6 +514,9 @@ class Sequence:
         self.cached_upto = 0
         self.cache_hash = 0
         self.text_sent = 0  # chars of decoded output already streamed
+        # guided decoding: guided.GuidedState (grammar + DFA state). Lives
+        # on the sequence, so it survives preemption and recompute
+        self.guided = None
 
     def __len__(self):
         return len(self.prompt_ids) + len(self.output_ids)
@@ -529,6 +573,11 @@ class LlmEngine:
         # multi-LoRA: models.lora.LoraBank built by start() when
         # cfg.lora_modules is set; None = every path below runs as before
         self.lora_bank = None
+        # guided decoding: guided.GuidedCompiler + guided.MaskBank built by
+        # start() when cfg.guided_decoding is set; None = off
+        self.guided_compiler = None
+        self.mask_bank = None
+        self._dead_end_logged = False
 
     # ------------------------------------------------------------------ #
     def start(self) -> None:
@@ -614,6 +663,8 @@ class LlmEngine:
 
         self.tokenizer = (HfTokenizer(cfg.tokenizer_path)
                           if cfg.tokenizer_path else SimpleTokenizer())
+        if cfg.guided_decoding:
+            self._start_guided(mcfg)
 
         # KV cache sizing from free HBM (heads sharded under TP)
         bs = cfg.block_size
@@ -671,6 +722,66 @@ class LlmEngine:
 
             self._plan_codec = PlanCodec(cfg, self.device)
         self._started = True
+
+    # ------------------------------------------------------------------ #
+    # guided decoding (guided.py; kernels ops/csrc/token_mask.hip)
+    # ------------------------------------------------------------------ #
+    def _start_guided(self, mcfg) -> None:
+        from .guided import GuidedCompiler, MaskBank
+
+        cfg = self.cfg
+        if self.tp_size > 1:
+            raise ValueError("guided_decoding is not supported under tensor "
+                             "parallelism (tp_size={})".format(self.tp_size))
+        if int(cfg.guided_mask_slots) < int(cfg.max_num_seqs):
+            raise ValueError(
+                "guided_mask_slots ({}) must be >= max_num_seqs ({}): one "
+                "step can need a mask per running sequence".format(
+                    cfg.guided_mask_slots, cfg.max_num_seqs))
+        # raises ValueError for tokenizers whose tokens are not bytes
+        self.guided_compiler = GuidedCompiler(
+            self.tokenizer, int(mcfg.vocab_size),
+            max_states=int(cfg.guided_max_states),
+            json_depth=int(cfg.guided_json_depth))
+        for key in ("guided_requests", "guided_mask_hits",
+                    "guided_mask_misses", "guided_dead_ends"):
+            self.stats[key] = 0
+        self.mask_bank = MaskBank(int(cfg.guided_mask_slots),
+                                  self.guided_compiler.vocab.words,
+                                  self.device, self.stats)
+
+    def _guided_state(self, params: SamplingParams):
+        """GuidedState for a request's constraint (compile is LRU-cached)."""
+        from .guided import GuidedState
+
+        if self.guided_compiler is None:
+            raise ValueError(
+                "this endpoint does not enable guided decoding (set "
+                "guided_decoding: true in the model card or aux config)")
+        if params.ignore_eos or params.min_tokens > 0:
+            raise ValueError("guided decoding cannot be combined with "
+                             "ignore_eos or min_tokens > 0")
+        grammar = self.guided_compiler.compile(*params.guided)
+        return GuidedState(grammar, [self.tokenizer.eos_id]
+                           + list(params.stop_token_ids))
+
+    def _note_dead_end(self, s: "Sequence") -> None:
+        self.stats["guided_dead_ends"] += 1
+        if not self._dead_end_logged:
+            self._dead_end_logged = True
+            print("[llm] guided decoding dead end: no token of the "
+                  "vocabulary continues grammar '{}' (further ones are "
+                  "only counted in stats)".format(s.guided.grammar.key[:80]))
+
+    def _finish_dead_end(self, s: "Sequence") -> None:
+        """A live grammar state whose mask allows no token (the vocabulary
+        cannot spell a required byte): finish instead of sampling."""
+        self._note_dead_end(s)
+        if not s.finished:
+            s.finished = True
+            s.finish_reason = "stop"
+            s.stream.put_nowait({"token_ids": [], "text": "",
+                                 "finished": True, "finish_reason": "stop"})
 
     # ------------------------------------------------------------------ #
     # multi-LoRA (models/lora.py; kernels ops/csrc/lora.hip)
@@ -751,6 +862,8 @@ class LlmEngine:
         if params.min_tokens > 0 and getattr(self, "tp_size", 1) > 1:
             raise ValueError(
                 "min_tokens is not supported under tensor parallelism yet")
+        guided_state = (self._guided_state(params)
+                        if params.guided is not None else None)
         if lora_idx >= 0:
             if self.lora_bank is None or lora_idx >= len(self.lora_bank):
                 raise ValueError("no LoRA adapter in slot {}".format(lora_idx))
@@ -760,6 +873,9 @@ class LlmEngine:
             self.stats["lora_requests"] += 1
         else:
             seq = Sequence(uuid.uuid4().hex, prompt_ids, params)
+        if guided_state is not None:
+            seq.guided = guided_state
+            self.stats["guided_requests"] += 1
         self.waiting.append(seq)
         self._ensure_loop()
         self._wake.set()
@@ -801,7 +917,8 @@ class LlmEngine:
         """Non-OpenAI route: {"prompt": str, "max_tokens": ...}; an
         optional "lora" key names a configured adapter."""
         prompt = body.get("prompt") or body.get("text") or ""
-        params = SamplingParams.from_request(body)
+        params = SamplingParams.from_request(
+            body, guided=self.cfg.guided_decoding)
         tokens: List[int] = []
         reason = None
         async for item in self.generate(prompt, params,
@@ -921,7 +1038,8 @@ class LlmEngine:
                 spec = [s for s in decoding if s.params.temperature == 0.0
                         and not s.params.has_penalties()
                         and s.params.logprobs is None
-                        and s.params.min_tokens <= s.generated]
+                        and s.params.min_tokens <= s.generated
+                        and s.guided is None]
                 rest = [s for s in decoding if s not in spec]
             else:
                 spec, rest = [], decoding
@@ -1833,27 +1951,109 @@ class LlmEngine:
             # call from run_tp_worker with the identical plan spec)
             next_ids = self._tp_sample_rows(
                 logits, sample or self._sample_spec(seqs))
+        elif self.mask_bank is not None \
+                and any(s.guided is not None for s in seqs):
+            self._sample_guided(seqs, logits)
+            return
         else:
-            logits = self._apply_penalties(logits, seqs)
-            # group rows by identical sampling params for batched kernels
-            # (a request-level seed gets its own group + generator)
-            groups: Dict[tuple, List[int]] = {}
-            for i, s in enumerate(seqs):
-                key = (s.params.temperature, s.params.top_k, s.params.top_p,
-                       s.params.seed)
-                groups.setdefault(key, []).append(i)
-            next_ids = torch.empty(len(seqs), dtype=torch.long)
-            for (temp, top_k, top_p, seed), idxs in groups.items():
-                rows = logits[idxs] if len(idxs) < len(seqs) else logits
-                gen = None
-                if seed is not None and temp != 0.0:
-                    s0 = seqs[idxs[0]]
-                    gen = torch.Generator(device=logits.device)
-                    gen.manual_seed((seed + s0.generated) & 0x7FFFFFFF)
-                sampled = ops.sample_top_k_top_p(
-                    rows, temperature=temp, top_k=top_k, top_p=top_p,
-                    generator=gen)
-                next_ids[idxs] = sampled.cpu()
+            logits, next_ids = self._sample_grouped(seqs, logits)
+        self._emit_sampled(seqs, next_ids, logits)
+
+    def _sample_grouped(self, seqs: List[Sequence], logits: torch.Tensor):
+        """Penalties, then one sampler launch per group of rows with
+        identical sampling params -> (post-penalty logits, next ids)."""
+        logits = self._apply_penalties(logits, seqs)
+        # group rows by identical sampling params for batched kernels
+        # (a request-level seed gets its own group + generator)
+        groups: Dict[tuple, List[int]] = {}
+        for i, s in enumerate(seqs):
+            key = (s.params.temperature, s.params.top_k, s.params.top_p,
+                   s.params.seed)
+            groups.setdefault(key, []).append(i)
+        next_ids = torch.empty(len(seqs), dtype=torch.long)
+        for (temp, top_k, top_p, seed), idxs in groups.items():
+            rows = logits[idxs] if len(idxs) < len(seqs) else logits
+            gen = None
+            if seed is not None and temp != 0.0:
+                s0 = seqs[idxs[0]]
+                gen = torch.Generator(device=logits.device)
+                gen.manual_seed((seed + s0.generated) & 0x7FFFFFFF)
+            sampled = ops.sample_top_k_top_p(
+                rows, temperature=temp, top_k=top_k, top_p=top_p,
+                generator=gen)
+            next_ids[idxs] = sampled.cpu()
+        return logits, next_ids
+
+    def _sample_guided(self, seqs: List[Sequence],
+                       logits: torch.Tensor) -> None:
+        """A step with at least one guided row (TP=1). Plain rows (no
+        top-k/top-p, penalties, logprobs or min_tokens ban) -- guided or
+        not -- go through ONE fused mask+draw launch with per-row
+        temperature and seed; the others are masked out of place and then
+        take the usual penalties -> grouped sampler -> logprobs flow, so
+        the mask applies before the penalties and logprobs are those of
+        the masked distribution."""
+        bank = self.mask_bank
+        bank.begin_step()
+        slots: List[int] = []
+        for s in seqs:
+            if s.guided is None:
+                slots.append(-1)
+            elif s.guided.num_allowed() == 0:
+                slots.append(-2)  # dead end: not sampled at all
+            else:
+                slots.append(bank.acquire(s.guided.key, s.guided.mask_words))
+        fused, rest = [], []
+        for i, s in enumerate(seqs):
+            p = s.params
+            if slots[i] == -2:
+                self._finish_dead_end(s)
+            elif (p.top_k > 0 or p.top_p < 1.0 or p.has_penalties()
+                  or p.logprobs is not None or p.min_tokens > s.generated):
+                rest.append(i)
+            else:
+                fused.append(i)
+        dev = logits.device
+
+        def rows_of(idxs):
+            return logits if len(idxs) == len(seqs) else logits[idxs]
+
+        fused_ids = rest_ids = rest_logits = None
+        if fused:
+            draws = torch.randint(0, 2**31 - 1, (len(fused),)).tolist()
+            seeds = [(seqs[i].params.seed + seqs[i].generated) & 0x7FFFFFFF
+                     if seqs[i].params.seed is not None else draws[j]
+                     for j, i in enumerate(fused)]
+            fused_ids = ops.sample_token_bitmask(
+                rows_of(fused), bank.bank,
+                torch.tensor([slots[i] for i in fused], dtype=torch.int32,
+                             device=dev),
+                torch.tensor([seqs[i].params.temperature for i in fused],
+                             dtype=torch.float32, device=dev),
+                torch.tensor(seeds, dtype=torch.int32, device=dev))
+        if rest:
+            masked = ops.apply_token_bitmask(
+                rows_of(rest), bank.bank,
+                torch.tensor([slots[i] for i in rest], dtype=torch.int32,
+                             device=dev))
+            rest_logits, rest_ids = self._sample_grouped(
+                [seqs[i] for i in rest], masked)
+        if fused:
+            fused_ids = fused_ids.cpu()
+            live = []
+            for j, i in enumerate(fused):
+                if int(fused_ids[j]) < 0:  # nothing finite to draw from
+                    self._finish_dead_end(seqs[i])
+                else:
+                    live.append(j)
+            self._emit_sampled([seqs[fused[j]] for j in live],
+                               fused_ids[live], None)
+        if rest:
+            self._emit_sampled([seqs[i] for i in rest], rest_ids,
+                               rest_logits)
+
+    def _emit_sampled(self, seqs: List[Sequence], next_ids: torch.Tensor,
+                      logits: Optional[torch.Tensor]) -> None:
         for i, s in enumerate(seqs):
             tok = int(next_ids[i])
             extra = None
@@ -1871,6 +2071,18 @@ class LlmEngine:
                         for v, t in zip(topv.tolist(), topi.tolist())}
                 extra = [e]
             self._emit_tokens(s, [tok], extras=extra)
+
+    def _guided_advance(self, s: Sequence, tok: int) -> bool:
+        """Move a guided sequence's DFA past ``tok``; True when the output
+        is complete -- accepting with nothing but eos left to say -- or the
+        grammar dead-ends, so no further step is spent on it."""
+        g = s.guided
+        g.advance(tok)
+        if g.num_continuations() > 0:
+            return False
+        if not g.accepting():
+            self._note_dead_end(s)
+        return True
 
     def _emit_tokens(self, s: Sequence, toks: List[int],
                      extras: Optional[List[Optional[dict]]] = None) -> None:
@@ -1891,6 +2103,8 @@ class LlmEngine:
             reason = None
             if (not s.params.ignore_eos and tok == eos) \
                     or tok in s.params.stop_token_ids:
+                finished, reason = True, "stop"
+            elif s.guided is not None and self._guided_advance(s, tok):
                 finished, reason = True, "stop"
             elif s.params.stop and self._hit_stop_string(s):
                 finished, reason = True, "stop"
@@ -1985,7 +2199,12 @@ class LlmEngine:
         semantics: n identical greedy choices are expected)."""
         out = []
         for i in range(n):
-            p = SamplingParams.from_request(body)
+            p = SamplingParams.from_request(
+                body, guided=self.cfg.guided_decoding)
+            if p.guided is not None and i == 0:
+                # compile now (LRU-cached for add_request): a grammar error
+                # must 422 before a streaming response has started
+                self._guided_state(p)
             if p.seed is not None:
                 p.seed = (p.seed + 7919 * i) & 0x7FFFFFFF
             out.append(p)

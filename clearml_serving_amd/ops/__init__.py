@@ -663,3 +663,81 @@ def lora_expand_add(y: torch.Tensor, b: torch.Tensor, idx: torch.Tensor,
     delta = torch.bmm(sel, yf.unsqueeze(-1)).squeeze(-1)
     out.copy_(torch.where(live, (out.float() + delta).to(out.dtype), out))
     return out
+
+
+# --------------------------------------------------------------------- #
+# Guided decoding: token bitmasks (kernels: csrc/token_mask.hip)
+# --------------------------------------------------------------------- #
+def _check_mask_args(logits: torch.Tensor, bank: torch.Tensor,
+                     slot: torch.Tensor) -> None:
+    if logits.dim() != 2:
+        raise ValueError("logits must be [B, V]")
+    if bank.dtype != torch.int32 or bank.dim() != 2 \
+            or bank.shape[1] != (logits.shape[1] + 31) // 32:
+        raise ValueError("bank must be int32 [S, ceil(V/32)]")
+    if slot.dtype != torch.int32 or slot.dim() != 1 \
+            or slot.shape[0] != logits.shape[0]:
+        raise ValueError("slot must be int32 [B]")
+
+
+def _unpack_token_bitmask(bank: torch.Tensor, slot: torch.Tensor,
+                          vocab: int) -> torch.Tensor:
+    """bool [B, V] allowed-token matrix; slot -1 rows are all True."""
+    rows = bank.index_select(0, slot.clamp(min=0).long())  # [B, W]
+    shifts = torch.arange(32, dtype=torch.int32, device=bank.device)
+    bits = (rows.unsqueeze(-1) >> shifts) & 1                # [B, W, 32]
+    allowed = bits.reshape(rows.shape[0], -1)[:, :vocab].bool()
+    return allowed | (slot < 0).unsqueeze(-1)
+
+
+def apply_token_bitmask(logits: torch.Tensor, bank: torch.Tensor,
+                        slot: torch.Tensor) -> torch.Tensor:
+    """Copy of ``logits`` [B, V] with the tokens its row's mask disallows
+    set to -inf; the source is never written (decode-graph logits are static
+    replay buffers).
+
+    bank: int32 [S, W], W = ceil(V/32), token t = bit t&31 of word t>>5;
+    slot: int32 [B] bank row per logits row, -1 = unconstrained (copied
+    bit-identically). PRECONDITION: slot < S (not checked on the GPU path --
+    that would cost a device sync; the kernel treats an out-of-range slot
+    as -1 rather than read past the bank)."""
+    if logits.is_cuda:
+        ext = _require_ext("apply_token_bitmask")
+        if ext is not None:
+            return ext.apply_token_bitmask(logits, bank, slot)
+    _check_mask_args(logits, bank, slot)
+    allowed = _unpack_token_bitmask(bank, slot, logits.shape[1])
+    return logits.masked_fill(~allowed, float("-inf"))
+
+
+def sample_token_bitmask(logits: torch.Tensor, bank: torch.Tensor,
+                         slot: torch.Tensor, temperature: torch.Tensor,
+                         seed: torch.Tensor) -> torch.Tensor:
+    """Fused mask + draw for a heterogeneous batch -> int64 [B].
+
+    temperature: float32 [B], 0 = greedy (argmax of the masked row, lowest
+    index on ties); otherwise one categorical draw from softmax(masked /
+    temperature), reproducible from that row's (logits, mask, temperature,
+    seed) alone -- independent of the row's position and of the batch.
+    seed: int32 [B]. A row whose mask allows nothing returns -1.
+
+    The CPU reference draws with torch.multinomial under a per-row
+    generator: same allowed set and greedy results as the GPU kernel, not
+    the same sampled tokens."""
+    if logits.is_cuda:
+        ext = _require_ext("sample_token_bitmask")
+        if ext is not None:
+            return ext.sample_token_bitmask(logits, bank, slot, temperature,
+                                            seed)
+    _check_mask_args(logits, bank, slot)
+    allowed = _unpack_token_bitmask(bank, slot, logits.shape[1])
+    masked = logits.float().masked_fill(~allowed, float("-inf"))
+    out = masked.argmax(dim=-1)
+    for i in range(logits.shape[0]):
+        t = float(temperature[i])
+        if t > 0.0 and bool(allowed[i].any()):
+            gen = torch.Generator(device=logits.device)
+            gen.manual_seed(int(seed[i]) & 0x7FFFFFFF)
+            probs = torch.softmax(masked[i] / t, dim=-1)
+            out[i] = torch.multinomial(probs, 1, generator=gen)[0]
+    return torch.where(allowed.any(dim=-1), out, torch.full_like(out, -1))

@@ -52,6 +52,12 @@ torch::Tensor conv3x3_nhwc(torch::Tensor x, torch::Tensor w,
 torch::Tensor lora_shrink(torch::Tensor x, torch::Tensor a, torch::Tensor idx);
 void lora_expand_add(torch::Tensor y, torch::Tensor b, torch::Tensor idx,
                      torch::Tensor out);
+torch::Tensor apply_token_bitmask(torch::Tensor logits, torch::Tensor bank,
+                                  torch::Tensor slot);
+torch::Tensor sample_token_bitmask(torch::Tensor logits, torch::Tensor bank,
+                                   torch::Tensor slot,
+                                   torch::Tensor temperature,
+                                   torch::Tensor seed);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "clearml-serving-amd gfx950 kernel library";
@@ -97,4 +103,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("idx"));
   m.def("lora_expand_add", &lora_expand_add, py::arg("y"), py::arg("b"),
         py::arg("idx"), py::arg("out"));
+  m.def("apply_token_bitmask", &apply_token_bitmask, py::arg("logits"),
+        py::arg("bank"), py::arg("slot"));
+  m.def("sample_token_bitmask", &sample_token_bitmask, py::arg("logits"),
+        py::arg("bank"), py::arg("slot"), py::arg("temperature"),
+        py::arg("seed"));
 }
