@@ -48,8 +48,12 @@ class Fp8Linear(nn.Module):
         self.register_buffer("weight_fp8", w8)
         # decode kernel reads a byte-swizzled copy (one 16-B lane load =
         # both MFMA operands of a 64-wide k pair); prefill scaled_mm needs
-        # the plain layout, so both live in HBM (fp8: still half of bf16)
-        self.register_buffer("weight_fp8_sw", ops.swizzle_fp8_weight(w8))
+        # the plain layout, so both live in HBM (fp8: still half of bf16).
+        # in_features % 64 != 0 never routes to that kernel (_route -> "lt")
+        # and has no swizzled form
+        self.register_buffer(
+            "weight_fp8_sw",
+            ops.swizzle_fp8_weight(w8) if w8.shape[1] % 64 == 0 else None)
         self.register_buffer("weight_scale",
                              scale.to(torch.float32).reshape(-1)
                              .contiguous())  # [N]

@@ -607,18 +607,25 @@ def skinny_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     small-N llama projections at M <= 16 (qkv 1.2x, o_proj 2.0-2.8x --
     hipBLASLt's tiles under-fill the 256-CU chip there) and the large-K
     down projection at M <= 2. Everything else falls back to
-    torch.nn.functional.linear (hipBLASLt).
+    torch.nn.functional.linear (hipBLASLt) -- as does an empty batch, and
+    a non-contiguous weight (the kernel streams W rows as stored; copying
+    a weight per call would cost more than the kernel saves).
     """
     if (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2
             and x.shape[1] % 32 == 0 and weight.shape[0] % 16 == 0
+            and weight.is_contiguous()
             and os.environ.get("CMLS_SKINNY", "1") != "0"):
         m, k = x.shape
         n = weight.shape[0]
         if ((1 <= m <= 16 and n <= 8192 and k <= 8192)
-                or (m <= 2 and n <= 8192)):
+                or (1 <= m <= 2 and n <= 8192)):
             ext = _require_ext("skinny_gemm")
-            if ext is not None:
-                return ext.skinny_gemm(x.contiguous(), weight, 1)
+            # the kernel's fragment loads are 16-byte vectors: a single row
+            # sliced at an odd column offset is "contiguous" yet misaligned
+            xc = x.contiguous()
+            if (ext is not None and xc.data_ptr() % 16 == 0
+                    and weight.data_ptr() % 16 == 0):
+                return ext.skinny_gemm(xc, weight, 1)
     return torch.nn.functional.linear(x, weight)
 
 

@@ -247,7 +247,10 @@ torch::Tensor skinny_gemm(torch::Tensor a, torch::Tensor w,
   TORCH_CHECK(a.dim() == 2 && w.dim() == 2, "skinny_gemm: 2-D only");
   TORCH_CHECK(a.scalar_type() == at::kBFloat16 &&
               w.scalar_type() == at::kBFloat16, "skinny_gemm: bf16 only");
-  TORCH_CHECK(a.stride(1) == 1 && a.stride(0) == a.size(1),
+  // is_contiguous(), not a stride comparison: a single row (decode M=1)
+  // sliced out of a wider tensor keeps the parent's row stride, which no
+  // kernel reads (rows >= M replay row 0)
+  TORCH_CHECK(a.is_contiguous(),
               "skinny_gemm: A must be row-major contiguous");
   TORCH_CHECK(w.is_contiguous(), "skinny_gemm: W must be contiguous");
   const int M = a.size(0), K = a.size(1), N = w.size(0);
