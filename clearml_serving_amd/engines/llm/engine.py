@@ -593,6 +593,8 @@ class LlmEngine:
         torch.manual_seed(1234)  # identical replicated params across ranks
         gpt2 = (str(cfg.arch).lower() == "gpt2"
                 or str(cfg.preset).startswith("gpt2"))
+        if not gpt2:
+            self._check_moe_options()
         lora_adapters = (self._load_lora_adapters(gpt2)
                          if cfg.lora_modules else None)
         if gpt2:
@@ -722,6 +724,42 @@ class LlmEngine:
 
             self._plan_codec = PlanCodec(cfg, self.device)
         self._started = True
+
+    def _check_moe_options(self) -> None:
+        """Refuse, before anything is built or read, what the MoE path does
+        not implement (cfg.overrides may declare an MoE of any size)."""
+        cfg = self.cfg
+        if "sliding_window" in cfg.overrides:
+            # applies to EVERY llama-family card, dense ones included (the
+            # field is not a LlamaConfig member, so it must not reach it):
+            # Mixtral cards carry it and released checkpoints set null,
+            # which is dropped from this engine's overrides; a window is
+            # refused for any model, since attention here is full-context
+            if cfg.overrides["sliding_window"] is not None:
+                raise ValueError(
+                    "sliding_window={} is not supported: attention here is "
+                    "full-context".format(cfg.overrides["sliding_window"]))
+            cfg.overrides = {k: v for k, v in cfg.overrides.items()
+                             if k != "sliding_window"}
+        base = PRESETS.get(cfg.preset)
+        n_exp = int(cfg.overrides.get(
+            "num_experts", base.num_experts if base is not None else 0))
+        if n_exp <= 0:
+            return
+        if cfg.quantization == "fp8":
+            raise ValueError(
+                "quantization='fp8' is not supported for mixture-of-experts "
+                "models (num_experts={}): the expert kernels are bf16".format(
+                    n_exp))
+        if cfg.lora_modules:
+            raise ValueError(
+                "lora_modules are not supported for mixture-of-experts "
+                "models (num_experts={})".format(n_exp))
+        if self.tp_size > 1:
+            raise ValueError(
+                "tensor parallelism (tp_size={}) is not supported for "
+                "mixture-of-experts models (num_experts={}): experts are "
+                "not sharded".format(self.tp_size, n_exp))
 
     # ------------------------------------------------------------------ #
     # guided decoding (guided.py; kernels ops/csrc/token_mask.hip)

@@ -92,6 +92,58 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor],
 convert_hf_qwen2 = convert_hf_llama
 
 
+def _is_hf_mixtral(hf: Dict[str, torch.Tensor]) -> bool:
+    return any(".block_sparse_moe.gate.weight" in k
+               or ".mlp.experts.gate_up_proj" in k for k in hf)
+
+
+def convert_hf_mixtral(hf: Dict[str, torch.Tensor],
+                       num_layers: int) -> Dict[str, torch.Tensor]:
+    """transformers MixtralForCausalLM -> models.llama.LlamaForCausalLM with
+    num_experts > 0. Accepts both key layouts found in the wild:
+
+    - hub checkpoints: ``block_sparse_moe.gate.weight`` and per-expert
+      ``block_sparse_moe.experts.{j}.w1|w3|w2.weight`` (w1 gate, w3 up,
+      w2 down);
+    - transformers' in-memory layout: ``mlp.gate.weight``,
+      ``mlp.experts.gate_up_proj`` [E, 2I, H], ``mlp.experts.down_proj``
+      [E, H, I] -- already the native stacking.
+    """
+    out = {
+        "embed.weight": hf["model.embed_tokens.weight"],
+        "final_norm": hf["model.norm.weight"],
+        "lm_head.weight": hf.get("lm_head.weight",
+                                 hf["model.embed_tokens.weight"]),
+    }
+    for i in range(num_layers):
+        p = "model.layers.{}.".format(i)
+        o = "layers.{}.".format(i)
+        out[o + "qkv.weight"] = torch.cat(
+            [hf[p + "self_attn.q_proj.weight"],
+             hf[p + "self_attn.k_proj.weight"],
+             hf[p + "self_attn.v_proj.weight"]], dim=0)
+        out[o + "o_proj.weight"] = hf[p + "self_attn.o_proj.weight"]
+        out[o + "attn_norm"] = hf[p + "input_layernorm.weight"]
+        out[o + "mlp_norm"] = hf[p + "post_attention_layernorm.weight"]
+        if p + "mlp.experts.gate_up_proj" in hf:
+            out[o + "router.weight"] = hf[p + "mlp.gate.weight"]
+            out[o + "w13"] = hf[p + "mlp.experts.gate_up_proj"]
+            out[o + "w2"] = hf[p + "mlp.experts.down_proj"]
+            continue
+        m = p + "block_sparse_moe."
+        out[o + "router.weight"] = hf[m + "gate.weight"]
+        n_exp = 0
+        while m + "experts.{}.w1.weight".format(n_exp) in hf:
+            n_exp += 1
+        out[o + "w13"] = torch.stack(
+            [torch.cat([hf[m + "experts.{}.w1.weight".format(j)],
+                        hf[m + "experts.{}.w3.weight".format(j)]], dim=0)
+             for j in range(n_exp)])
+        out[o + "w2"] = torch.stack(
+            [hf[m + "experts.{}.w2.weight".format(j)] for j in range(n_exp)])
+    return out
+
+
 def convert_hf_gpt2(hf: Dict[str, torch.Tensor],
                     num_layers: int) -> Dict[str, torch.Tensor]:
     """transformers GPT2LMHeadModel -> models.gpt2.GPT2ForCausalLM.
@@ -129,7 +181,7 @@ def convert_hf_gpt2(hf: Dict[str, torch.Tensor],
 
 def convert_hf_auto(hf: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """Detect a raw HuggingFace state dict by its key layout and convert it
-    to the matching native layout (llama/qwen2, gpt2, or bert). Native-
+    to the matching native layout (llama/qwen2, mixtral, gpt2, or bert). Native-
     layout dicts pass through unchanged -- callers can always route
     through this."""
     def n_layers(prefix, probe):
@@ -141,6 +193,8 @@ def convert_hf_auto(hf: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
 
     keys = hf.keys()
     if any(k.startswith("model.embed_tokens.") for k in keys):
+        if _is_hf_mixtral(hf):  # before llama: same attention key names
+            return convert_hf_mixtral(hf, n_layers("model.layers.", "."))
         return convert_hf_llama(hf, n_layers("model.layers.", "."))
     if any("wte.weight" in k for k in keys) and \
             any(".attn.c_attn." in k for k in keys):

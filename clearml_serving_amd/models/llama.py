@@ -40,6 +40,11 @@ class LlamaConfig:
     max_position: int = 8192
     tie_embeddings: bool = False
     qkv_bias: bool = False  # Qwen2-family checkpoints carry QKV biases
+    # mixture of experts (Mixtral): 0 = dense MLP. With experts the MLP is a
+    # router + top-k routed SwiGLU experts (ops.moe_route / ops.moe_experts)
+    num_experts: int = 0
+    experts_per_tok: int = 2
+    norm_topk_prob: bool = True  # renormalize the k routing weights
 
     @property
     def head_dim(self) -> int:
@@ -67,8 +72,17 @@ class LlamaLayer(nn.Module):
         self.qkv = nn.Linear(h, q_out + 2 * kv_out, bias=cfg.qkv_bias)
         self.o_proj = nn.Linear(q_out, h, bias=False)
         self.mlp_norm = nn.Parameter(torch.ones(h))
-        self.gate_up = nn.Linear(h, 2 * inter, bias=False)
-        self.down = nn.Linear(inter, h, bias=False)
+        if cfg.num_experts > 0:
+            assert tp_size == 1, "experts are not sharded: MoE serves at tp=1"
+            # expert stacks in the layout the grouped GEMMs stream: w13[e]
+            # is gate rows then up rows, both [out, in] like nn.Linear
+            self.router = nn.Linear(h, cfg.num_experts, bias=False)
+            self.w13 = nn.Parameter(
+                torch.empty(cfg.num_experts, 2 * inter, h))
+            self.w2 = nn.Parameter(torch.empty(cfg.num_experts, h, inter))
+        else:
+            self.gate_up = nn.Linear(h, 2 * inter, bias=False)
+            self.down = nn.Linear(inter, h, bias=False)
         self.inter = inter
 
     @staticmethod
@@ -185,6 +199,14 @@ class LlamaLayer(nn.Module):
         """norm -> gate_up -> silu*up -> down, WITHOUT the row-parallel
         all-reduce (see attn_half). ``lora``: attn_ctx["lora"] or None."""
         cfg = self.cfg
+        if cfg.num_experts > 0:
+            # norm -> router -> routed experts; every launch is sync-free,
+            # so the block captures into the decode graphs
+            x = ops.rmsnorm(attn_out, self.mlp_norm, cfg.rms_eps,
+                            residual=residual)
+            ids, weights = ops.moe_route(self.router(x), cfg.experts_per_tok,
+                                         cfg.norm_topk_prob)
+            return ops.moe_experts(x, self.w13, self.w2, ids, weights)
         fp8 = not isinstance(self.qkv, nn.Linear)
         if fp8:
             x8, xs = ops.rmsnorm_fp8(attn_out, self.mlp_norm, cfg.rms_eps,
@@ -232,6 +254,12 @@ class LlamaForCausalLM(nn.Module):
                 nn.init.normal_(m.weight, std=std)
             elif isinstance(m, nn.Embedding):
                 nn.init.normal_(m.weight, std=std)
+        # expert stacks are bare Parameters, which modules() does not visit;
+        # drawn after the loop, so dense models consume the RNG as before
+        for layer in self.layers:
+            if self.cfg.num_experts > 0:
+                nn.init.normal_(layer.w13, std=std)
+                nn.init.normal_(layer.w2, std=std)
 
     def forward(
         self,
@@ -335,6 +363,18 @@ PRESETS = {
                               rope_theta=1e6, rms_eps=1e-6,
                               max_position=32768, qkv_bias=True,
                               tie_embeddings=True),
+    # Mixtral: llama attention + 8 SwiGLU experts, top-2 routing
+    # (models/convert.py convert_hf_mixtral; numerics pinned vs transformers
+    # in tests/test_moe_cpu.py). 8x7B is ~93 GB in bf16: one MI355X.
+    "mixtral-8x7b": LlamaConfig(vocab_size=32000, hidden=4096, layers=32,
+                                heads=32, kv_heads=8, intermediate=14336,
+                                rope_theta=1e6, rms_eps=1e-5,
+                                max_position=32768, num_experts=8,
+                                experts_per_tok=2),
+    "mixtral-tiny": LlamaConfig(vocab_size=512, hidden=256, layers=2, heads=4,
+                                kv_heads=2, intermediate=512,
+                                rope_theta=10000.0, max_position=512,
+                                num_experts=4, experts_per_tok=2),
 }
 
 

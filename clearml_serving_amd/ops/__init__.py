@@ -748,3 +748,221 @@ def sample_token_bitmask(logits: torch.Tensor, bank: torch.Tensor,
             probs = torch.softmax(masked[i] / t, dim=-1)
             out[i] = torch.multinomial(probs, 1, generator=gen)[0]
     return torch.where(allowed.any(dim=-1), out, torch.full_like(out, -1))
+
+
+# --------------------------------------------------------------------- #
+# Mixture of experts (kernels: csrc/moe.hip). The plain-PyTorch references
+# below DEFINE the semantics the kernels are tested against.
+# --------------------------------------------------------------------- #
+MOE_MAX_EXPERTS = 64
+MOE_MAX_TOP_K = 8
+
+
+def _check_moe_route(num_experts: int, top_k: int) -> None:
+    if not (1 <= top_k <= MOE_MAX_TOP_K
+            and top_k <= num_experts <= MOE_MAX_EXPERTS):
+        raise RuntimeError(
+            "moe: need 1 <= k <= {} and k <= E <= {}, got k={} E={}".format(
+                MOE_MAX_TOP_K, MOE_MAX_EXPERTS, top_k, num_experts))
+
+
+def moe_nb_max(num_slots: int, num_experts: int, block_m: int) -> int:
+    """Row blocks moe_align reserves: the worst case over all routings of
+    sum_e ceil(count_e / block_m) -- a function of shapes only."""
+    return ((num_slots + min(num_experts, num_slots) * (block_m - 1))
+            // block_m)
+
+
+def moe_route(logits: torch.Tensor, top_k: int,
+              renormalize: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Router: logits [T, E] (bf16 or fp32) -> (ids int32 [T, k], weights
+    fp32 [T, k]).
+
+    Reference semantics (this function's CPU path): softmax over all E
+    experts in fp32; the top-k experts are selected by LOGIT order (monotonic
+    with the probabilities), a tie going to the lowest expert index, and
+    emitted in descending probability; ``renormalize`` divides the k weights
+    by their sum (Mixtral). 1 <= k <= 8 and k <= E <= 64, else RuntimeError.
+    """
+    _check_moe_route(logits.shape[-1], top_k)
+    if logits.is_cuda:
+        ext = _require_ext("moe_route")
+        if ext is not None:
+            ids, weights = ext.moe_route(logits.contiguous(), int(top_k),
+                                         bool(renormalize))
+            return ids, weights
+    lf = logits.float()
+    probs = torch.softmax(lf, dim=-1)
+    # a stable descending sort keeps the lowest index first among equals
+    ids = torch.sort(lf, dim=-1, descending=True,
+                     stable=True).indices[:, :top_k]
+    weights = probs.gather(-1, ids)
+    if renormalize:
+        weights = weights / weights.sum(dim=-1, keepdim=True)
+    return ids.to(torch.int32), weights
+
+
+def moe_align(ids: torch.Tensor, num_experts: int,
+              block_m: int = 16) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Group the S = T*k flat slots (slot = t*k + j) of ``ids`` int32 [T, k]
+    by expert for the grouped GEMMs -> (sorted_slots int32 [NB_max*block_m],
+    block_expert int32 [NB_max]), NB_max = moe_nb_max(S, E, block_m).
+
+    Reference semantics (this function's CPU path): experts in ascending
+    order, each expert's slots ascending and padded to a multiple of
+    ``block_m`` rows with the sentinel S; ``block_expert[b]`` is the expert
+    of rows [b*block_m, (b+1)*block_m); unused trailing blocks hold -1 (and
+    sentinel rows). Every slot appears exactly once. PRECONDITION: ids in
+    [0, E) -- not checked on the GPU path (a device sync); the kernel drops
+    a slot whose id is out of range."""
+    if not 1 <= num_experts <= MOE_MAX_EXPERTS:
+        raise RuntimeError("moe_align: need 1 <= E <= {}, got {}".format(
+            MOE_MAX_EXPERTS, num_experts))
+    if ids.is_cuda:
+        ext = _require_ext("moe_align")
+        if ext is not None:
+            sorted_slots, block_expert = ext.moe_align(
+                ids.contiguous(), int(num_experts), int(block_m))
+            return sorted_slots, block_expert
+    flat = ids.reshape(-1)
+    s = flat.numel()
+    nb_max = moe_nb_max(s, num_experts, block_m)
+    sorted_slots = torch.full((nb_max * block_m,), s, dtype=torch.int32,
+                              device=ids.device)
+    block_expert = torch.full((nb_max,), -1, dtype=torch.int32,
+                              device=ids.device)
+    blk = 0
+    for e in range(num_experts):
+        slots = (flat == e).nonzero().flatten()
+        c = slots.numel()
+        if c == 0:
+            continue
+        nb = (c + block_m - 1) // block_m
+        sorted_slots[blk * block_m: blk * block_m + c] = slots.to(torch.int32)
+        block_expert[blk: blk + nb] = e
+        blk += nb
+    return sorted_slots, block_expert
+
+
+def _moe_experts_ref(x, w13, w2, ids, weights, act_dtype=None):
+    """fp32 per-expert loop. ``act_dtype`` rounds silu(g)*u to that dtype
+    first, the one place the fused path stores an intermediate in bf16."""
+    t, h = x.shape
+    inter = w2.shape[2]
+    k = ids.shape[1]
+    xf = x.float()
+    y = torch.zeros(t, k, h, dtype=torch.float32, device=x.device)
+    for e in range(w13.shape[0]):
+        tok, choice = (ids == e).nonzero(as_tuple=True)
+        if tok.numel() == 0:
+            continue
+        gu = xf[tok] @ w13[e].float().t()
+        act = torch.nn.functional.silu(gu[:, :inter]) * gu[:, inter:]
+        if act_dtype is not None:
+            act = act.to(act_dtype).float()
+        y[tok, choice] = act @ w2[e].float().t()
+    out = torch.zeros(t, h, dtype=torch.float32, device=x.device)
+    for j in range(k):  # ascending j, fp32, one rounding at the end
+        out += weights[:, j, None].float() * y[:, j]
+    return out.to(x.dtype)
+
+
+# Rows (tokens) up to which the fused grouped-GEMM path serves a GPU call
+# outside graph capture; above it the call runs the per-expert hipBLASLt
+# loop. From the Mixtral-8x7B layer table in profiles/moe_bench.txt: fused
+# (64-row block) 1008 us vs loop 1419 us at T=128, 1654 vs 1510 us at T=256.
+MOE_FUSED_MAX = int(os.environ.get("CMLS_MOE_FUSED_MAX", "128"))
+# Row block of the fused path: 16 rows up to this many tokens, 64 above
+# (same table: 720 vs 856 us at T=64, 1252 vs 1008 us at T=128).
+MOE_BLOCK16_MAX = int(os.environ.get("CMLS_MOE_BLOCK16_MAX", "64"))
+
+
+def _moe_experts_loop(x, w13, w2, ids, weights):
+    """Prefill-sized GPU path: per-expert hipBLASLt GEMMs in the model
+    dtype. Reads the per-expert row sets back to the host, so it is not
+    capturable; moe_experts never routes here under graph capture.
+
+    Same combine as the fused path (fp32 sum in ascending j, one rounding),
+    but the GEMMs are hipBLASLt's: the down projection is rounded to bf16
+    before the combine and its accumulation order follows the row count, so
+    results agree with the fused path to bf16 tolerance, not bit for bit."""
+    t, h = x.shape
+    inter = w2.shape[2]
+    k = ids.shape[1]
+    y = torch.zeros(t, k, h, dtype=torch.float32, device=x.device)
+    for e in range(w13.shape[0]):
+        tok, choice = (ids == e).nonzero(as_tuple=True)
+        if tok.numel() == 0:
+            continue
+        gu = torch.nn.functional.linear(x[tok], w13[e])
+        act = silu_mul(gu[:, :inter].contiguous(), gu[:, inter:].contiguous())
+        y[tok, choice] = torch.nn.functional.linear(act, w2[e]).float()
+    out = torch.zeros(t, h, dtype=torch.float32, device=x.device)
+    for j in range(k):
+        out += weights[:, j, None] * y[:, j]
+    return out.to(x.dtype)
+
+
+def moe_experts(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
+                ids: torch.Tensor, weights: torch.Tensor,
+                block_m: Optional[int] = None) -> torch.Tensor:
+    """Routed SwiGLU expert FFN: out[t] = sum_j weights[t, j] *
+    (silu(x[t] @ Wg^T) * (x[t] @ Wu^T)) @ W2^T with the matrices of expert
+    ids[t, j] -> [T, H] in x's dtype.
+
+    x: [T, H]; w13: [E, 2I, H] (gate rows then up rows); w2: [E, H, I];
+    ids int32 [T, k] and weights fp32 [T, k] from moe_route. The sum over j
+    runs in fp32 in ascending j with one final rounding.
+
+    Reference semantics (CPU path): an fp32 per-expert loop. GPU: bf16,
+    H % 32 == 0, I % 32 == 0, k <= E <= 64, contiguous 16-byte-aligned
+    operands, else RuntimeError. The fused path (csrc/moe.hip) is sync-free
+    and is the only path under graph capture; it stores silu(g)*u once in
+    bf16. ``block_m`` (16 or 64) forces its row block; None picks the path
+    and block from the measured thresholds above.
+
+    Bit-reproducibility and batch invariance (a token's output does not
+    depend on the other rows) hold WITHIN the fused path, for either row
+    block. Outside capture a call with T > MOE_FUSED_MAX runs the
+    per-expert hipBLASLt loop instead, whose results agree to bf16
+    tolerance only: a token's bits can change when its batch crosses that
+    threshold (prefill vs decode), as they do for every dense projection
+    that switches between skinny_linear and hipBLASLt.
+
+    PRECONDITION: ids in [0, E). Not checked on the GPU (a device sync).
+    No access goes out of bounds for a bad id, but moe_align drops that
+    slot, its expert output is never written, and the token's result is
+    then undefined (the fused path reads an uninitialised row).
+    """
+    if x.is_cuda:
+        ext = _require_ext("moe_experts")
+        if ext is not None:
+            t = x.shape[0]
+            if block_m is None:
+                if (t > MOE_FUSED_MAX
+                        and not torch.cuda.is_current_stream_capturing()):
+                    _check_moe_shapes(x, w13, w2, ids)
+                    return _moe_experts_loop(x, w13, w2, ids, weights)
+                block_m = 16 if t <= MOE_BLOCK16_MAX else 64
+            return ext.moe_experts(x, w13, w2, ids, weights, int(block_m))
+    return _moe_experts_ref(x, w13, w2, ids, weights)
+
+
+def _check_moe_shapes(x, w13, w2, ids) -> None:
+    """The fused kernel's shape contract, held on the loop path too so that
+    what a shape does never depends on T."""
+    h, inter, e, k = x.shape[1], w2.shape[2], w13.shape[0], ids.shape[1]
+    if h % 32 or inter % 32 or not (k <= e <= MOE_MAX_EXPERTS):
+        raise RuntimeError(
+            "moe_experts: need H % 32 == 0, I % 32 == 0 and k <= E <= {}, "
+            "got H={} I={} E={} k={}".format(MOE_MAX_EXPERTS, h, inter, e, k))
+
+
+def moe_ffn(x: torch.Tensor, router_weight: torch.Tensor, w13: torch.Tensor,
+            w2: torch.Tensor, top_k: int,
+            renormalize: bool = True) -> torch.Tensor:
+    """Whole MoE block: router logits = x @ router_weight^T ([E, H]), then
+    moe_route and moe_experts."""
+    logits = torch.nn.functional.linear(x, router_weight)
+    ids, weights = moe_route(logits, top_k, renormalize)
+    return moe_experts(x, w13, w2, ids, weights)

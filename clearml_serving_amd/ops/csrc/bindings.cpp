@@ -58,6 +58,13 @@ torch::Tensor sample_token_bitmask(torch::Tensor logits, torch::Tensor bank,
                                    torch::Tensor slot,
                                    torch::Tensor temperature,
                                    torch::Tensor seed);
+std::vector<torch::Tensor> moe_route(torch::Tensor logits, int64_t top_k,
+                                     bool renormalize);
+std::vector<torch::Tensor> moe_align(torch::Tensor ids, int64_t num_experts,
+                                     int64_t block_m);
+torch::Tensor moe_experts(torch::Tensor x, torch::Tensor w13, torch::Tensor w2,
+                          torch::Tensor ids, torch::Tensor weights,
+                          int64_t block_m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "clearml-serving-amd gfx950 kernel library";
@@ -108,4 +115,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_token_bitmask", &sample_token_bitmask, py::arg("logits"),
         py::arg("bank"), py::arg("slot"), py::arg("temperature"),
         py::arg("seed"));
+  m.def("moe_route", &moe_route, py::arg("logits"), py::arg("top_k"),
+        py::arg("renormalize") = true);
+  m.def("moe_align", &moe_align, py::arg("ids"), py::arg("num_experts"),
+        py::arg("block_m") = 16);
+  m.def("moe_experts", &moe_experts, py::arg("x"), py::arg("w13"),
+        py::arg("w2"), py::arg("ids"), py::arg("weights"),
+        py::arg("block_m") = 16);
 }

@@ -17,6 +17,10 @@ The model is TRAINED (not random): it memorizes a pangram continuation,
 which the tests then reproduce greedily through the full serving path.
 
     python examples/llm/make_tiny_checkpoint.py OUTDIR [--steps 300]
+
+``--moe E`` trains a Mixtral-style mixture of E experts (top-2 routing)
+instead; hf_model.safetensors then carries transformers' Mixtral keys and
+the card declares ``num_experts``.
 """
 
 import argparse
@@ -56,6 +60,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("outdir")
     ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--moe", type=int, default=0, metavar="E",
+                    help="train a Mixtral-style MoE with E experts (top-2)")
     args = ap.parse_args()
     os.makedirs(args.outdir, exist_ok=True)
 
@@ -64,7 +70,7 @@ def main():
     from transformers import LlamaConfig as HfLlamaConfig
     from transformers import LlamaForCausalLM as HfLlama
 
-    from clearml_serving_amd.models.convert import convert_hf_llama
+    from clearml_serving_amd.models.convert import convert_hf_auto
 
     tok_path = train_tokenizer(args.outdir)
     from tokenizers import Tokenizer
@@ -79,7 +85,19 @@ def main():
         num_attention_heads=4, num_key_value_heads=2, intermediate_size=512,
         max_position_embeddings=256, rope_theta=10000.0, rms_norm_eps=1e-5,
         tie_word_embeddings=False, attention_bias=False, mlp_bias=False)
-    model = HfLlama(cfg)
+    if args.moe:
+        from transformers import MixtralConfig, MixtralForCausalLM
+
+        cfg = MixtralConfig(
+            vocab_size=vocab_padded, hidden_size=256, num_hidden_layers=2,
+            num_attention_heads=4, num_key_value_heads=2,
+            intermediate_size=512, max_position_embeddings=256,
+            rope_theta=10000.0, rms_norm_eps=1e-5, tie_word_embeddings=False,
+            num_local_experts=args.moe, num_experts_per_tok=2,
+            sliding_window=None)
+        model = MixtralForCausalLM(cfg)
+    else:
+        model = HfLlama(cfg)
 
     # train: next-token prediction over the pangram corpus until the model
     # reproduces the memorized continuation greedily
@@ -116,7 +134,7 @@ def main():
     hf_state = {k: v.contiguous() for k, v in model.state_dict().items()
                 if not k.endswith("rotary_emb.inv_freq")}
     save_file(hf_state, os.path.join(args.outdir, "hf_model.safetensors"))
-    native = convert_hf_llama(hf_state, num_layers=2)
+    native = convert_hf_auto(hf_state)
     save_file({k: v.contiguous() for k, v in native.items()},
               os.path.join(args.outdir, "model.safetensors"))
     with open(os.path.join(args.outdir, "model_card.json"), "wt") as f:
@@ -125,7 +143,9 @@ def main():
             "overrides": {"vocab_size": vocab_padded, "hidden": 256,
                           "layers": 2, "heads": 4, "kv_heads": 2,
                           "intermediate": 512, "rope_theta": 10000.0,
-                          "max_position": 256},
+                          "max_position": 256,
+                          **({"num_experts": args.moe, "experts_per_tok": 2}
+                             if args.moe else {})},
             "max_model_len": 192, "block_size": 16, "num_kv_blocks": 128,
             "memorized": memorized,
         }, f, indent=1)
