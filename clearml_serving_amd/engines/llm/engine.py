@@ -361,6 +361,12 @@ class LlmEngineConfig:
         return cfg
 
 
+# seq.blocks entry of a page that sliding-window reclamation has returned
+# to the allocator: the list keeps its logical indexing, every consumer
+# skips the sentinel, and plans carry a valid page id in its place
+FREED_BLOCK = -1
+
+
 class BlockAllocator:
     def __init__(self, num_blocks: int):
         self.num_blocks = num_blocks
@@ -503,6 +509,8 @@ class Sequence:
         self.prefilled = 0  # prompt tokens already in the KV cache
         self.params = params
         self.blocks: List[int] = []
+        # sliding window: blocks[:swa_freed] are FREED_BLOCK sentinels
+        self.swa_freed = 0
         self.stream: "asyncio.Queue" = asyncio.Queue()
         self.finished = False
         self.finish_reason: Optional[str] = None
@@ -569,10 +577,13 @@ class LlmEngine:
                       "preemptions": 0, "aborts": 0,
                       "graph_captures": 0, "graph_replays": 0,
                       "spec_proposed": 0, "spec_accepted": 0,
-                      "lora_requests": 0}
+                      "lora_requests": 0, "swa_blocks_freed": 0}
         # multi-LoRA: models.lora.LoraBank built by start() when
         # cfg.lora_modules is set; None = every path below runs as before
         self.lora_bank = None
+        # sliding-window width of the served model (LlamaConfig), set by
+        # start(); 0 = full context, no KV page reclamation
+        self._window = 0
         # guided decoding: guided.GuidedCompiler + guided.MaskBank built by
         # start() when cfg.guided_decoding is set; None = off
         self.guided_compiler = None
@@ -593,6 +604,7 @@ class LlmEngine:
         torch.manual_seed(1234)  # identical replicated params across ranks
         gpt2 = (str(cfg.arch).lower() == "gpt2"
                 or str(cfg.preset).startswith("gpt2"))
+        self._check_sliding_window(gpt2)
         if not gpt2:
             self._check_moe_options()
         lora_adapters = (self._load_lora_adapters(gpt2)
@@ -623,6 +635,7 @@ class LlmEngine:
             mcfg = LlamaConfig(**{**PRESETS[cfg.preset].__dict__,
                                   **cfg.overrides})
             self.model_config = mcfg
+            self._window = int(mcfg.sliding_window)
             model = LlamaForCausalLM(mcfg, tp_rank=self.tp_rank,
                                      tp_size=self.tp_size)
         if cfg.weights:
@@ -725,27 +738,45 @@ class LlmEngine:
             self._plan_codec = PlanCodec(cfg, self.device)
         self._started = True
 
+    def _check_sliding_window(self, gpt2: bool) -> None:
+        """Validate a ``sliding_window`` override before anything is built.
+        Model cards carry the key with null for full context (released
+        Mixtral cards do): null is dropped so the preset's value stands."""
+        cfg = self.cfg
+        if "sliding_window" not in cfg.overrides:
+            return
+        window = cfg.overrides["sliding_window"]
+        if window is None:
+            cfg.overrides = {k: v for k, v in cfg.overrides.items()
+                             if k != "sliding_window"}
+            return
+        if gpt2:
+            raise ValueError(
+                "sliding_window={} is not supported for arch=gpt2: the "
+                "window is implemented for the llama family".format(window))
+        if isinstance(window, bool) or not isinstance(window, int) \
+                or window < 0:
+            raise ValueError(
+                "sliding_window must be a non-negative integer or null, "
+                "got {!r}".format(window))
+
     def _check_moe_options(self) -> None:
         """Refuse, before anything is built or read, what the MoE path does
         not implement (cfg.overrides may declare an MoE of any size)."""
         cfg = self.cfg
-        if "sliding_window" in cfg.overrides:
-            # applies to EVERY llama-family card, dense ones included (the
-            # field is not a LlamaConfig member, so it must not reach it):
-            # Mixtral cards carry it and released checkpoints set null,
-            # which is dropped from this engine's overrides; a window is
-            # refused for any model, since attention here is full-context
-            if cfg.overrides["sliding_window"] is not None:
-                raise ValueError(
-                    "sliding_window={} is not supported: attention here is "
-                    "full-context".format(cfg.overrides["sliding_window"]))
-            cfg.overrides = {k: v for k, v in cfg.overrides.items()
-                             if k != "sliding_window"}
         base = PRESETS.get(cfg.preset)
         n_exp = int(cfg.overrides.get(
             "num_experts", base.num_experts if base is not None else 0))
         if n_exp <= 0:
             return
+        window = cfg.overrides.get(
+            "sliding_window", base.sliding_window if base is not None else 0)
+        if window:
+            # dense cards only: the windowed path is not validated against
+            # a Mixtral reference, and released Mixtral cards set null
+            raise ValueError(
+                "sliding_window={} is not supported for mixture-of-experts "
+                "models (num_experts={})".format(window, n_exp))
         if cfg.quantization == "fp8":
             raise ValueError(
                 "quantization='fp8' is not supported for mixture-of-experts "
@@ -1024,9 +1055,7 @@ class LlmEngine:
                 for seq in self.waiting + self.running:
                     seq.stream.put_nowait(
                         {"error": str(ex), "finished": True, "token_ids": []})
-                    if seq.blocks:
-                        self.allocator.free(seq.blocks)
-                        seq.blocks = []
+                    self._free_blocks(seq)
                 self.waiting.clear()
                 self.running.clear()
                 raise
@@ -1089,8 +1118,48 @@ class LlmEngine:
             self._register_prefix(s)  # publish newly-FILLED blocks
             if s.finished:
                 self.running.remove(s)
-                self.allocator.free(s.blocks)
-                s.blocks = []
+                self._free_blocks(s)
+            else:
+                # after _register_prefix, so a page is published (and stays
+                # matchable) before it goes back through allocator.free
+                self._reclaim_window(s)
+
+    def _free_blocks(self, seq: Sequence) -> None:
+        """Return every page the sequence still holds (window-reclaimed
+        entries were freed when they became sentinels)."""
+        held = [b for b in seq.blocks if b != FREED_BLOCK]
+        if held:
+            self.allocator.free(held)
+        seq.blocks = []
+        seq.swa_freed = 0
+
+    def _reclaim_window(self, s: Sequence) -> None:
+        """Sliding window: free the pages no future query of ``s`` can see.
+        The next query sits at position p (the next chunk's first position
+        mid-prefill, else the newest token, whose K/V is written on its
+        step); it and every later query see only keys > p - window, so
+        page j is dead once (j + 1) * block_size <= p - window + 1."""
+        if not self._window or not s.blocks:
+            return
+        if s.prefilled < len(s.prompt_ids):
+            p = s.prefilled
+        else:
+            p = len(s) - 1
+        dead = min((p - self._window + 1) // self.cfg.block_size,
+                   len(s.blocks))
+        if dead <= s.swa_freed:
+            return
+        self.allocator.free(s.blocks[s.swa_freed:dead])
+        s.blocks[s.swa_freed:dead] = [FREED_BLOCK] * (dead - s.swa_freed)
+        self.stats["swa_blocks_freed"] += dead - s.swa_freed
+        s.swa_freed = dead
+
+    @staticmethod
+    def _block_table(s: Sequence) -> List[int]:
+        """Block-table row for a plan (TP codec, device tables, decode-graph
+        statics): window-reclaimed entries, which the kernels never read,
+        carry page 0 so the table holds only in-range ids."""
+        return [0 if b == FREED_BLOCK else b for b in s.blocks]
 
     def _drain_aborts(self) -> None:
         """Apply aborts queued by abort() -- all scheduler-state mutation
@@ -1104,9 +1173,7 @@ class LlmEngine:
                 self.waiting.remove(seq)
             if seq in self.running:
                 self.running.remove(seq)
-            if seq.blocks:
-                self.allocator.free(seq.blocks)
-                seq.blocks = []
+            self._free_blocks(seq)
 
     def _admit(self) -> List[Sequence]:
         admitted: List[Sequence] = []
@@ -1137,6 +1204,7 @@ class LlmEngine:
                     self.allocator.free(cached)
                 break
             seq.blocks = cached + self.allocator.alloc(need_blocks)
+            seq.swa_freed = 0
             seq.prefilled = ncached  # cached prefix skips its prefill
             # registration chain restarts at the match point (also resets
             # stale state on preemption re-admission)
@@ -1173,14 +1241,24 @@ class LlmEngine:
         toks = s.prompt_ids + s.output_ids
         while s.cached_upto + bs <= avail:
             blk = s.cached_upto // bs
-            s.cache_hash = alloc.register_block(
-                s.cache_hash, toks[s.cached_upto:s.cached_upto + bs],
-                s.blocks[blk])
+            tokens = toks[s.cached_upto:s.cached_upto + bs]
+            if s.blocks[blk] == FREED_BLOCK:
+                # window-reclaimed before it was published (cannot happen in
+                # step order; kept safe): only the chain hash advances
+                s.cache_hash = hash((s.cache_hash, tuple(tokens)))
+            else:
+                s.cache_hash = alloc.register_block(
+                    s.cache_hash, tokens, s.blocks[blk])
             s.cached_upto += bs
 
     def _slot(self, seq: Sequence, pos: int) -> int:
         bs = self.cfg.block_size
-        return seq.blocks[pos // bs] * bs + pos % bs
+        blk = seq.blocks[pos // bs]
+        if blk == FREED_BLOCK:
+            raise RuntimeError(
+                "position {} lies in a page the sliding window already "
+                "reclaimed".format(pos))
+        return blk * bs + pos % bs
 
     def _sample_spec(self, seqs: List[Sequence]) -> List[tuple]:
         step_seed = random.getrandbits(31)
@@ -1256,7 +1334,7 @@ class LlmEngine:
             "slots": [[self._slot(s, p)
                        for p in range(s.prefilled, s.prefilled + c)]
                       for s, c in batch],
-            "blocks": [list(s.blocks) for s, c in batch],
+            "blocks": [self._block_table(s) for s, c in batch],
             "complete": [s.prefilled + c >= len(s.prompt_ids)
                          for s, c in batch],
         }
@@ -1408,8 +1486,7 @@ class LlmEngine:
             return False
         victim = max(candidates, key=lambda s: s.created)
         self.running.remove(victim)
-        self.allocator.free(victim.blocks)
-        victim.blocks = []
+        self._free_blocks(victim)
         victim.prompt_ids = victim.prompt_ids + victim.output_ids
         victim.output_ids = []
         self.waiting.insert(0, victim)
@@ -1448,7 +1525,7 @@ class LlmEngine:
             "positions": [len(s) - 1 for s in seqs],
             "slots": [self._slot(s, len(s) - 1) for s in seqs],
             "seq_lens": [len(s) for s in seqs],
-            "blocks": [list(s.blocks) for s in seqs],
+            "blocks": [self._block_table(s) for s in seqs],
             "sample": self._sample_spec(seqs),
         }
         if self.lora_bank is not None:
@@ -1628,7 +1705,7 @@ class LlmEngine:
             "slots": [[self._slot(s, p)
                        for p in range(len(s) - 1, len(s) + len(prop))]
                       for s, prop in zip(seqs, proposals)],
-            "blocks": [list(s.blocks) for s in seqs],
+            "blocks": [self._block_table(s) for s in seqs],
         }
         if self.lora_bank is not None:
             plan["lora"] = [s.lora_idx for s in seqs]

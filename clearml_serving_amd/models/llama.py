@@ -45,6 +45,9 @@ class LlamaConfig:
     num_experts: int = 0
     experts_per_tok: int = 2
     norm_topk_prob: bool = True  # renormalize the k routing weights
+    # sliding-window attention (Mistral): position i sees keys j with
+    # i - sliding_window < j <= i; 0 = full context
+    sliding_window: int = 0
 
     @property
     def head_dim(self) -> int:
@@ -163,13 +166,15 @@ class LlamaLayer(nn.Module):
                                attn_ctx["slot_mapping"], k_sc, v_sc)
 
         scale = 1.0 / math.sqrt(self.head_dim)
+        window = cfg.sliding_window  # model constant, same on every rank
         if attn_ctx["mode"] == "prefill":
             b, s = attn_ctx["batch"], attn_ctx["seq"]
             qb = q.unflatten(0, (b, s))  # [B, S, H, D] strided views
             kb = k.unflatten(0, (b, s))
             vb = v.unflatten(0, (b, s))
             ctx = ops.attention(qb, kb, vb, causal=True, scale=scale,
-                                seq_lens=attn_ctx["seq_lens"], layout="bshd")
+                                seq_lens=attn_ctx["seq_lens"], layout="bshd",
+                                window=window)
             ctx = ctx.reshape(t, self.heads * self.head_dim)
         elif attn_ctx["mode"] == "prefill_paged":
             # chunked prefill: this chunk's queries attend to the full paged
@@ -178,12 +183,14 @@ class LlamaLayer(nn.Module):
             ctx = ops.attention_prefill_paged(
                 q.unflatten(0, (b, s)), k_cache, v_cache,
                 attn_ctx["block_table"], attn_ctx["kv_lens"],
-                attn_ctx["q_lens"], scale=scale, k_scale=k_sc, v_scale=v_sc)
+                attn_ctx["q_lens"], scale=scale, k_scale=k_sc, v_scale=v_sc,
+                window=window)
             ctx = ctx.reshape(t, self.heads * self.head_dim)
         else:  # decode: one token per sequence
             ctx = ops.attention_decode(
                 q, k_cache, v_cache, attn_ctx["block_table"],
-                attn_ctx["seq_lens"], scale=scale, k_scale=k_sc, v_scale=v_sc)
+                attn_ctx["seq_lens"], scale=scale, k_scale=k_sc, v_scale=v_sc,
+                window=window)
             ctx = ctx.view(t, self.heads * self.head_dim)
         if fp8:
             # attention context has no fused producer: one-pass dynamic quant
@@ -375,6 +382,18 @@ PRESETS = {
                                 kv_heads=2, intermediate=512,
                                 rope_theta=10000.0, max_position=512,
                                 num_experts=4, experts_per_tok=2),
+    # Mistral-7B-v0.1: llama tensor names (convert_hf_llama) + a 4096-key
+    # sliding window (numerics pinned vs transformers in
+    # tests/test_sliding_window_cpu.py)
+    "mistral-7b": LlamaConfig(vocab_size=32000, hidden=4096, layers=32,
+                              heads=32, kv_heads=8, intermediate=14336,
+                              rope_theta=10000.0, rms_eps=1e-5,
+                              max_position=32768, sliding_window=4096),
+    # window 24 on purpose: the default 16-token KV page does not divide it
+    "mistral-tiny": LlamaConfig(vocab_size=512, hidden=256, layers=2, heads=4,
+                                kv_heads=2, intermediate=512,
+                                rope_theta=10000.0, max_position=512,
+                                sliding_window=24),
 }
 
 

@@ -304,11 +304,22 @@ def softmax(x: torch.Tensor, dim: int = -1) -> torch.Tensor:
 # --------------------------------------------------------------------- #
 # Attention
 # --------------------------------------------------------------------- #
+def _check_window(window: Optional[int]) -> int:
+    """Sliding-window argument -> kernel convention (0 = full context)."""
+    if window is None:
+        return 0
+    window = int(window)
+    if window < 0:
+        raise ValueError("window must be >= 0, got {}".format(window))
+    return window
+
+
 def attention(
     q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     causal: bool = False, scale: Optional[float] = None,
     seq_lens: Optional[torch.Tensor] = None,
     layout: str = "bhsd",
+    window: Optional[int] = None,
 ) -> torch.Tensor:
     """Fused scaled-dot-product attention (prefill / encoder).
 
@@ -316,19 +327,25 @@ def attention(
     (strided views into a merged QKV projection are accepted -- no
     transpose copies). GQA via H_kv dividing H; ``seq_lens`` (int32 [B])
     masks keys >= len. Output has the input layout.
+
+    ``window`` (sliding-window attention, causal only): query position i
+    sees key j iff ``i - window < j <= i``; None or 0 = full context.
     """
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    window = _check_window(window)
+    if window and not causal:
+        raise ValueError("attention: a sliding window needs causal=True")
     bshd = layout == "bshd"
     if q.is_cuda:
         ext = _require_ext("attention")
         if ext is not None:
             return ext.attention_prefill(q, k, v, bool(causal), float(scale),
-                                         seq_lens, bshd)
+                                         seq_lens, bshd, window)
     if bshd:
         out = attention(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3),
                         v.permute(0, 2, 1, 3), causal=causal, scale=scale,
-                        seq_lens=seq_lens)
+                        seq_lens=seq_lens, window=window)
         return out.permute(0, 2, 1, 3).contiguous()
     # reference path (fp32 math)
     qf, kf, vf = q.float(), k.float(), v.float()
@@ -342,6 +359,12 @@ def attention(
     if causal:
         mask = torch.ones(sq, sk, dtype=torch.bool, device=q.device).tril(
             diagonal=sk - sq)
+        if window:
+            # query row r sits at position r + (sk - sq); it keeps the
+            # `window` most recent keys, its own included
+            mask &= ~torch.ones(sq, sk, dtype=torch.bool,
+                                device=q.device).tril(
+                diagonal=sk - sq - window)
         scores = scores.masked_fill(~mask, float("-inf"))
     if seq_lens is not None:
         key_idx = torch.arange(sk, device=q.device)
@@ -364,27 +387,33 @@ def attention_prefill_paged(
     scale: Optional[float] = None,
     k_scale: Optional[torch.Tensor] = None,
     v_scale: Optional[torch.Tensor] = None,
+    window: Optional[int] = None,
 ) -> torch.Tensor:
     """Chunked-prefill attention: chunk queries [B, Sq, H, D] (bshd) attend
     causally to the full PAGED history (kv_lens keys per seq, already in the
     cache); q_lens masks per-seq chunk padding. Output [B, Sq, H, D].
+
+    ``window``: sliding window as in :func:`attention`. Pages that lie
+    wholly below the window start of a sequence's first query are never
+    read, so their block-table entries may point at any valid page.
 
     fp8 KV: uint8 e4m3 caches + per-token-per-head ``k_scale``/``v_scale``
     float32 [NB, Hkv, BS]; the gfx950 kernel dequantizes while staging tiles
     to LDS (attention.hip FP8KV)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    window = _check_window(window)
     if q.is_cuda:
         ext = _require_ext("attention_prefill_paged")
         if ext is not None:
             return ext.attention_prefill_paged(
                 q, k_cache, v_cache, block_table, kv_lens, q_lens,
-                float(scale), k_scale, v_scale)
+                float(scale), k_scale, v_scale, window)
     if k_scale is not None:
         return attention_prefill_paged(
             q, _dequant_kv_cpu(k_cache, k_scale),
             _dequant_kv_cpu(v_cache, v_scale), block_table, kv_lens, q_lens,
-            scale)
+            scale, window=window)
     # reference path: gather pages -> dense causal attention with history
     b, sq, h, d = q.shape
     hkv = k_cache.shape[1]
@@ -399,9 +428,14 @@ def attention_prefill_paged(
             hkv, nb * bs, d)[:, :n]
         v = v_cache[blocks].float().permute(1, 0, 2, 3).reshape(
             hkv, nb * bs, d)[:, :n]
+        if window:
+            # keys below the first query's window are masked for every
+            # row; their pages may be recycled, so drop them unread
+            lo = max(0, n - ql - window + 1)
+            k, v = k[:, lo:], v[:, lo:]
         o = attention(
             q[i, :ql].permute(1, 0, 2)[None].float(),
-            k[None], v[None], causal=True, scale=scale)
+            k[None], v[None], causal=True, scale=scale, window=window)
         out[i, :ql] = o[0].permute(1, 0, 2).to(q.dtype)
     return out
 
@@ -412,6 +446,7 @@ def attention_decode(
     scale: Optional[float] = None,
     k_scale: Optional[torch.Tensor] = None,
     v_scale: Optional[torch.Tensor] = None,
+    window: Optional[int] = None,
 ) -> torch.Tensor:
     """Paged-KV decode attention: one new token per sequence.
 
@@ -423,19 +458,24 @@ def attention_decode(
 
     fp8 KV: uint8 e4m3 caches + float32 [NB, Hkv, BS] per-token scales;
     halves the decode KV-read bytes (the long-context bandwidth bound).
+
+    ``window``: the query sees only the last ``window`` keys (None or 0 =
+    all of them); keys and block-table entries below that are never read.
     """
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    window = _check_window(window)
     if q.is_cuda:
         ext = _require_ext("attention_decode")
         if ext is not None:
             return ext.attention_decode(q, k_cache, v_cache, block_table,
                                         seq_lens, float(scale),
-                                        k_scale, v_scale)
+                                        k_scale, v_scale, window)
     if k_scale is not None:
         return attention_decode(
             q, _dequant_kv_cpu(k_cache, k_scale),
-            _dequant_kv_cpu(v_cache, v_scale), block_table, seq_lens, scale)
+            _dequant_kv_cpu(v_cache, v_scale), block_table, seq_lens, scale,
+            window=window)
     # reference path: gather pages then dense attention per sequence
     bsz, hq, d = q.shape
     hkv = k_cache.shape[1]
@@ -451,6 +491,8 @@ def attention_decode(
         v = v_cache[blocks].float()
         k = k.permute(1, 0, 2, 3).reshape(hkv, nblocks * block_size, d)[:, :n]
         v = v.permute(1, 0, 2, 3).reshape(hkv, nblocks * block_size, d)[:, :n]
+        if window:
+            k, v = k[:, max(0, n - window):], v[:, max(0, n - window):]
         if rep > 1:
             k = k.repeat_interleave(rep, dim=0)
             v = v.repeat_interleave(rep, dim=0)

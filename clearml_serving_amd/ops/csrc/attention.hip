@@ -38,6 +38,11 @@
 // with a causal history offset), paged KV, fp8 (e4m3) paged KV dequantized
 // at stage time. bf16 in/out, fp32 accumulate.
 //
+// Sliding window (WINDOW, causal only): query position p sees key j iff
+// p - window < j <= p. The key loop starts at the tile holding the window
+// start of the block's FIRST row; keys below that start are never loaded
+// (the engine may have recycled their pages) and stage as zeros.
+//
 // Measured and removed (docs/ROADMAP.md "Measured dead ends",
 // profiles/attn_v2_ab.txt): the S = mfma(Q, K) kernel with P in LDS
 // (1.10-1.18x slower), reading K fragments straight from global instead of
@@ -84,7 +89,7 @@ __device__ __forceinline__ void fp8x4_to_bf16(int w, float sc, short* o) {
 }
 
 template <int HEAD_DIM, bool CAUSAL, bool HAS_SEQLENS, bool PAGED = false,
-          bool FP8KV = false>
+          bool FP8KV = false, bool WINDOW = false>
 __global__ __launch_bounds__(NWAVES * 64, 2) void attn_prefill_kernel(
     const __hip_bfloat16* __restrict__ q,   // [B, H, Sq, D] via strides
     const void* __restrict__ kvoid,   // bf16 dense via strides, or paged
@@ -100,7 +105,8 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_prefill_kernel(
     const int* __restrict__ block_table,    // [B, max_blocks] when PAGED
     int block_size, int max_blocks,
     AttnStrides st,
-    int B, int H, int Hkv, int Sq, int Sk, float scale) {
+    int B, int H, int Hkv, int Sq, int Sk, float scale, int window) {
+  static_assert(!WINDOW || CAUSAL, "a sliding window implies causal");
   // softmax in the exp2 domain: v_exp_f32 IS 2^x, so folding log2(e) into
   // the score scale deletes one full-rate VALU mul per exp call
   const float scale2 = scale * 1.4426950408889634f;
@@ -149,6 +155,10 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_prefill_kernel(
   // (history offset = kv_len - q_len)
   const int causal_off = kv_len - q_len;
   const int kv_hi = CAUSAL ? min(kv_len, m0 + BLOCK_M + causal_off) : kv_len;
+  // sliding window: first key any row of this block sees (its first row's
+  // window start), and the tile that holds it
+  const int win_first = WINDOW ? max(0, m0 + causal_off - window + 1) : 0;
+  const int kv_lo = WINDOW ? (win_first & ~(BLOCK_N - 1)) : 0;
   const int* btab = PAGED ? block_table + (long)b * max_blocks : nullptr;
 
   const int frag_row = lane & 15;       // q column (and K key-in-tile)
@@ -187,7 +197,7 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_prefill_kernel(
       const int p = tid + i * NWAVES * 64;
       const int gkey = n0 + p / (D / 8);
       const int d8 = (p % (D / 8)) * 8;
-      if (gkey < kv_len) {
+      if (gkey < kv_len && (!WINDOW || gkey >= win_first)) {
         long off;
         long blk = 0;
         if (PAGED) {
@@ -268,9 +278,11 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_prefill_kernel(
     // interior tiles (every key valid for every query of the block) skip
     // masking entirely: run on every tile, the per-element compare+select
     // chain measured ~20% of the kernel's VALU work
+    // (windowed: the block's LAST row has the highest window start)
     const bool tile_full =
         (n0 + BLOCK_N <= kv_len) &&
-        (!CAUSAL || (n0 + BLOCK_N - 1 <= m0 + causal_off));
+        (!CAUSAL || (n0 + BLOCK_N - 1 <= m0 + causal_off)) &&
+        (!WINDOW || (n0 > m0 + BLOCK_M - 1 + causal_off - window));
     float pv[BLOCK_N / 16][4];
     float rmax = -INFINITY;
     if (tile_full) {
@@ -292,6 +304,7 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_prefill_kernel(
           float s = acc_s[t][r] * scale2;
           bool valid = key < kv_len;
           if (CAUSAL) valid = valid && (key <= qrow + causal_off);
+          if (WINDOW) valid = valid && (key > qrow + causal_off - window);
           s = valid ? s : -INFINITY;
           pv[t][r] = s;
           rmax = fmaxf(rmax, s);
@@ -303,6 +316,8 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_prefill_kernel(
     rmax = fmaxf(rmax, __shfl_xor(rmax, 32, 64));
     const float m_new = fmaxf(m_run, rmax);
     // all-masked columns keep m = -inf; exp() yields 0 contributions
+    // (pad rows, and with a window the high rows of a block on its first
+    // tiles: both guards below keep exp2(-inf - -inf) out of the state)
     const float alpha =
         (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - m_new);
     float rsum = 0.f;
@@ -384,11 +399,11 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_prefill_kernel(
   };
 
   // ================= KV tile loop ================= //
-  stage_load(0);
+  stage_load(kv_lo);
   stage_write(0);
   __syncthreads();
   int cur = 0;
-  for (int n0 = 0; n0 < kv_hi; n0 += BLOCK_N) {
+  for (int n0 = kv_lo; n0 < kv_hi; n0 += BLOCK_N) {
     // issue next tile's global loads now; they complete under this tile's
     // MFMA + softmax work
     const bool has_next = n0 + BLOCK_N < kv_hi;
@@ -427,7 +442,7 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_prefill_kernel(
 torch::Tensor attention_prefill(torch::Tensor q, torch::Tensor k,
                                 torch::Tensor v, bool causal, double scale,
                                 c10::optional<torch::Tensor> seq_lens,
-                                bool bshd) {
+                                bool bshd, int64_t window) {
   TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
               "q/k/v must be 4-D");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "attention: bf16 only");
@@ -440,6 +455,11 @@ torch::Tensor attention_prefill(torch::Tensor q, torch::Tensor k,
   const int Hkv = k.size(hdim), Sk = k.size(sdim);
   TORCH_CHECK(H % Hkv == 0, "H must be a multiple of H_kv");
   TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
+  TORCH_CHECK(window >= 0, "window must be >= 0");
+  TORCH_CHECK(window == 0 || causal, "a sliding window needs causal=True");
+  // a window that covers every key is the windowless kernel
+  const bool win = window > 0 && window < Sk;
+  const int W = win ? (int)window : 0;
   TORCH_CHECK(v.size(hdim) == Hkv && v.size(sdim) == Sk && v.size(3) == D);
   TORCH_CHECK(k.stride(0) == v.stride(0) && k.stride(1) == v.stride(1) &&
               k.stride(2) == v.stride(2), "k/v must share layout");
@@ -460,14 +480,18 @@ torch::Tensor attention_prefill(torch::Tensor q, torch::Tensor k,
   dim3 grid(B * H, (Sq + BLOCK_M - 1) / BLOCK_M);
   dim3 block(NWAVES * 64);
   hipStream_t stream_ = cmls::current_stream();
-#define LAUNCH_ATTN(DD, CC, SS)                                              \
-  hipLaunchKernelGGL((attn_prefill_kernel<DD, CC, SS>), grid, block, 0,      \
-                     stream_, (const __hip_bfloat16*)q.data_ptr(),           \
-                     (const void*)k.data_ptr(),                              \
-                     (const void*)v.data_ptr(), nullptr, nullptr,            \
-                     (__hip_bfloat16*)out.data_ptr(), sl, nullptr, nullptr,  \
-                     0, 0, st, B, H, Hkv, Sq, Sk, (float)scale)
-  if (D == 64) {
+#define LAUNCH_ATTN_W(DD, CC, SS, WW)                                        \
+  hipLaunchKernelGGL(                                                        \
+      (attn_prefill_kernel<DD, CC, SS, false, false, WW>), grid, block, 0,   \
+      stream_, (const __hip_bfloat16*)q.data_ptr(),                          \
+      (const void*)k.data_ptr(), (const void*)v.data_ptr(), nullptr,         \
+      nullptr, (__hip_bfloat16*)out.data_ptr(), sl, nullptr, nullptr, 0, 0,  \
+      st, B, H, Hkv, Sq, Sk, (float)scale, W)
+#define LAUNCH_ATTN(DD, CC, SS) LAUNCH_ATTN_W(DD, CC, SS, false)
+  if (win) {
+    if (D == 64) { if (sl) LAUNCH_ATTN_W(64, true, true, true); else LAUNCH_ATTN_W(64, true, false, true); }
+    else         { if (sl) LAUNCH_ATTN_W(128, true, true, true); else LAUNCH_ATTN_W(128, true, false, true); }
+  } else if (D == 64) {
     if (causal) { if (sl) LAUNCH_ATTN(64, true, true); else LAUNCH_ATTN(64, true, false); }
     else        { if (sl) LAUNCH_ATTN(64, false, true); else LAUNCH_ATTN(64, false, false); }
   } else {
@@ -475,6 +499,7 @@ torch::Tensor attention_prefill(torch::Tensor q, torch::Tensor k,
     else        { if (sl) LAUNCH_ATTN(128, false, true); else LAUNCH_ATTN(128, false, false); }
   }
 #undef LAUNCH_ATTN
+#undef LAUNCH_ATTN_W
   return out;
 }
 
@@ -487,7 +512,8 @@ torch::Tensor attention_prefill_paged(
     torch::Tensor q_lens,       // int32 [B] valid query rows per sequence
     double scale,
     c10::optional<torch::Tensor> k_scale,   // float [NB, Hkv, BS] (fp8 KV)
-    c10::optional<torch::Tensor> v_scale) {
+    c10::optional<torch::Tensor> v_scale,
+    int64_t window) {                       // sliding window, 0 = off
   // chunked-prefill attention: the chunk's queries attend causally to the
   // full paged history + the chunk itself (K/V already scattered into the
   // cache by kv_cache_write before this call).
@@ -522,20 +548,28 @@ torch::Tensor attention_prefill_paged(
   st.ob = out.stride(0); st.oh = out.stride(2); st.os = out.stride(1);
   // Sk bound for the kv loop = max kv_len; kernel clamps per sequence
   const int Sk = kl.max().item<int>();
+  TORCH_CHECK(window >= 0, "window must be >= 0");
+  // a window that covers the longest sequence is the windowless kernel
+  const bool win = window > 0 && window < Sk;
+  const int W = win ? (int)window : 0;
   dim3 grid(B * H, (Sq + BLOCK_M - 1) / BLOCK_M);
   dim3 block(NWAVES * 64);
   hipStream_t stream_ = cmls::current_stream();
-#define LAUNCH_PAGED(DD, F8)                                                 \
+#define LAUNCH_PAGED_W(DD, F8, WW)                                           \
   hipLaunchKernelGGL(                                                        \
-      (attn_prefill_kernel<DD, true, true, true, F8>),                       \
+      (attn_prefill_kernel<DD, true, true, true, F8, WW>),                   \
       grid, block, 0, stream_, (const __hip_bfloat16*)q.data_ptr(),          \
       (const void*)k_cache.data_ptr(), (const void*)v_cache.data_ptr(),      \
       kscp, vscp, (__hip_bfloat16*)out.data_ptr(), kl.data_ptr<int>(),       \
       ql.data_ptr<int>(), bt.data_ptr<int>(), BS, max_blocks,                \
-      st, B, H, Hkv, Sq, Sk, (float)scale)
+      st, B, H, Hkv, Sq, Sk, (float)scale, W)
+#define LAUNCH_PAGED(DD, F8)                                                 \
+  do { if (win) LAUNCH_PAGED_W(DD, F8, true);                                \
+       else LAUNCH_PAGED_W(DD, F8, false); } while (0)
   if (D == 64) { if (fp8kv) LAUNCH_PAGED(64, true); else LAUNCH_PAGED(64, false); }
   else         { if (fp8kv) LAUNCH_PAGED(128, true); else LAUNCH_PAGED(128, false); }
 #undef LAUNCH_PAGED
+#undef LAUNCH_PAGED_W
   return out;
 }
 #endif  // CMLS_KERNEL_ONLY

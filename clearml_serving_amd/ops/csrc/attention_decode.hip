@@ -67,7 +67,16 @@ typedef __attribute__((ext_vector_type(2))) unsigned int uint32x2_t;
 // ([NB, Hkv, BS] f32) -- halves the KV HBM stream AND doubles the cached
 // tokens per GB; scores/values dequantize inline (VALU headroom exists:
 // the kernel is HBM-bound at 3.4-4.9 TB/s).
-template <int D, int GQ, int UNROLL = 4, int MINB = 2, bool FP8KV = false>
+//
+// WINDOW (sliding-window attention): the query, at position total_keys-1,
+// sees only the last `window` keys. The key range is [win_lo, total_keys)
+// and the flash-decoding splits partition THAT range, so the kernel streams
+// at most `window` keys per sequence however long the context is. Keys and
+// block-table entries below win_lo are never read (the engine recycles
+// those pages): split 0 simply starts its 16-key iterations at win_lo,
+// which needs no alignment -- a group's load is one whole key row.
+template <int D, int GQ, int UNROLL = 4, int MINB = 2, bool FP8KV = false,
+          bool WINDOW = false>
 __global__ __launch_bounds__(256, MINB) void attn_decode_kernel(
     const __hip_bfloat16* __restrict__ q,        // [B, H, D]
     const void* __restrict__ k_cache,            // [NB, Hkv, BS, D] bf16|e4m3
@@ -80,7 +89,8 @@ __global__ __launch_bounds__(256, MINB) void attn_decode_kernel(
     float* __restrict__ partial_o,               // [B, H, SPLITS, D] f32
     float* __restrict__ partial_ml,              // [B, H, SPLITS, 2] f32
     int splits, long q_bstride,
-    int H, int Hkv, int block_size, int max_blocks, float scale) {
+    int H, int Hkv, int block_size, int max_blocks, float scale,
+    int window) {
   // softmax in the exp2 domain (v_exp_f32 is 2^x; log2e folds into scale)
   const float scale2 = scale * 1.4426950408889634f;
   constexpr int NW = 4;        // waves
@@ -96,9 +106,10 @@ __global__ __launch_bounds__(256, MINB) void attn_decode_kernel(
   const int sub = lane & 15;          // d-slice owner
   const int split = blockIdx.z;
   const int total_keys = seq_lens[b];
+  const int win_lo = WINDOW ? max(0, total_keys - window) : 0;
   // chunk rounded to the 16-key workgroup iteration so splits don't overlap
-  const int chunk = ((total_keys + splits - 1) / splits + 15) & ~15;
-  const int key_lo = split * chunk;
+  const int chunk = ((total_keys - win_lo + splits - 1) / splits + 15) & ~15;
+  const int key_lo = win_lo + split * chunk;
   const int n_keys = min(total_keys, key_lo + chunk);
   if (key_lo >= total_keys && split > 0) {
     // empty split: publish a neutral partial (m=-inf skips it in combine)
@@ -449,8 +460,14 @@ torch::Tensor attention_decode(torch::Tensor q, torch::Tensor k_cache,
                                torch::Tensor block_table,
                                torch::Tensor seq_lens, double scale,
                                c10::optional<torch::Tensor> k_scale,
-                               c10::optional<torch::Tensor> v_scale) {
+                               c10::optional<torch::Tensor> v_scale,
+                               int64_t window) {  // sliding window, 0 = off
   TORCH_CHECK(q.dim() == 3, "q must be [B, H, D]");
+  TORCH_CHECK(window >= 0, "window must be >= 0");
+  // a window no sequence of this table can outgrow is the windowless kernel
+  const bool win =
+      window > 0 && window < block_table.size(1) * k_cache.size(2);
+  const int W = win ? (int)window : 0;
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "decode attention: bf16 only");
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == q.size(2),
               "q heads must be dense");
@@ -497,18 +514,20 @@ torch::Tensor attention_decode(torch::Tensor q, torch::Tensor k_cache,
   }
   dim3 grid(B, Hkv, splits);
 
-#define LAUNCH_DEC(DD, GG, UU, MM, F8)                                       \
-  hipLaunchKernelGGL((attn_decode_kernel<DD, GG, UU, MM, F8>), grid,         \
+#define LAUNCH_DEC(DD, GG, UU, MM, F8, WW)                                   \
+  hipLaunchKernelGGL((attn_decode_kernel<DD, GG, UU, MM, F8, WW>), grid,     \
                      dim3(256), 0,                                           \
                      stream_, (const __hip_bfloat16*)q.data_ptr(),           \
                      (const void*)k_cache.data_ptr(),                        \
                      (const void*)v_cache.data_ptr(), ksp, vsp,              \
                      bt.data_ptr<int>(), sl.data_ptr<int>(),                 \
                      (__hip_bfloat16*)out.data_ptr(), po, pml, splits,       \
-                     q.stride(0), H, Hkv, BS, max_blocks, (float)scale)
+                     q.stride(0), H, Hkv, BS, max_blocks, (float)scale, W)
 #define LAUNCH_DEC_F(DD, GG, UU, MM)                                         \
-  do { if (fp8kv) LAUNCH_DEC(DD, GG, UU, MM, true);                          \
-       else LAUNCH_DEC(DD, GG, UU, MM, false); } while (0)
+  do { if (win) { if (fp8kv) LAUNCH_DEC(DD, GG, UU, MM, true, true);         \
+                  else LAUNCH_DEC(DD, GG, UU, MM, false, true); }            \
+       else { if (fp8kv) LAUNCH_DEC(DD, GG, UU, MM, true, false);            \
+              else LAUNCH_DEC(DD, GG, UU, MM, false, false); } } while (0)
   // GQ 3/5/6/7 (qwen2-7b is 28q/4kv = 7, qwen2-1.5b 12q/2kv = 6) run the
   // same kernel with shallower UNROLL: per-group accumulator arrays
   // (o_acc[GQ][8] + score[UNROLL][GQ]) scale VGPRs linearly with GQ

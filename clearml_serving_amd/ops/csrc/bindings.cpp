@@ -14,7 +14,7 @@ torch::Tensor softmax_lastdim(torch::Tensor x);
 torch::Tensor attention_prefill(torch::Tensor q, torch::Tensor k,
                                 torch::Tensor v, bool causal, double scale,
                                 c10::optional<torch::Tensor> seq_lens,
-                                bool bshd);
+                                bool bshd, int64_t window);
 torch::Tensor sample_top_k_top_p(torch::Tensor logits, double temperature,
                                  long top_k, double top_p, long seed);
 torch::Tensor attention_decode(torch::Tensor q, torch::Tensor k_cache,
@@ -22,7 +22,8 @@ torch::Tensor attention_decode(torch::Tensor q, torch::Tensor k_cache,
                                torch::Tensor block_table,
                                torch::Tensor seq_lens, double scale,
                                c10::optional<torch::Tensor> k_scale,
-                               c10::optional<torch::Tensor> v_scale);
+                               c10::optional<torch::Tensor> v_scale,
+                               int64_t window);
 void kv_cache_write(torch::Tensor knew, torch::Tensor vnew,
                     torch::Tensor k_cache, torch::Tensor v_cache,
                     torch::Tensor slot_mapping,
@@ -34,7 +35,7 @@ torch::Tensor attention_prefill_paged(
     torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
     torch::Tensor block_table, torch::Tensor kv_lens, torch::Tensor q_lens,
     double scale, c10::optional<torch::Tensor> k_scale,
-    c10::optional<torch::Tensor> v_scale);
+    c10::optional<torch::Tensor> v_scale, int64_t window);
 void rope_inplace(torch::Tensor q, torch::Tensor k, torch::Tensor positions,
                   double theta);
 std::vector<torch::Tensor> rmsnorm_fp8(torch::Tensor x, torch::Tensor weight,
@@ -80,13 +81,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_lastdim", &softmax_lastdim);
   m.def("attention_prefill", &attention_prefill, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("causal"), py::arg("scale"),
-        py::arg("seq_lens") = py::none(), py::arg("bshd") = false);
+        py::arg("seq_lens") = py::none(), py::arg("bshd") = false,
+        py::arg("window") = 0);
   m.def("sample_top_k_top_p", &sample_top_k_top_p);
   m.def("rope_inplace", &rope_inplace);
   m.def("attention_decode", &attention_decode, py::arg("q"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
         py::arg("seq_lens"), py::arg("scale"),
-        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(),
+        py::arg("window") = 0);
   m.def("kv_cache_write", &kv_cache_write, py::arg("knew"), py::arg("vnew"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("slot_mapping"),
         py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
@@ -96,7 +99,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_prefill_paged", &attention_prefill_paged, py::arg("q"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
         py::arg("kv_lens"), py::arg("q_lens"), py::arg("scale"),
-        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(),
+        py::arg("window") = 0);
   m.def("rmsnorm_fp8", &rmsnorm_fp8, py::arg("x"), py::arg("weight"),
         py::arg("eps") = 1e-6, py::arg("residual") = py::none());
   m.def("silu_mul_fp8", &silu_mul_fp8);
