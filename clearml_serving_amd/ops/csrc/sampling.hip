@@ -49,7 +49,10 @@ __global__ void gumbel_argmax_kernel(const T* __restrict__ logits,
     const float lg = to_f32(lrow[idx]);
     if (lg == -INFINITY) continue;  // filtered token
     const unsigned int h = pcg_hash(row_seed + (unsigned)idx);
-    const float u = ((float)h + 1.0f) * (1.0f / 4294967296.0f);
+    // 23 hash bits + 0.5 is exact in fp32: u in [2^-24, 1 - 2^-24], never
+    // 0 or 1, so g is finite ((float)h + 1 rounded the top 128 hashes up to
+    // u == 1 and g == +inf). Same arithmetic as token_mask.hip.
+    const float u = ((float)(h >> 9) + 0.5f) * (1.0f / 8388608.0f);
     const float g = -__logf(-__logf(u));
     const float s = lg * inv_temp + g;
     if (s > bv) { bv = s; bi = idx; }

@@ -130,7 +130,9 @@ struct Best {
     float s = lg;
     if (inv_temp != 0.0f) {
       const unsigned int h = tm_pcg_hash(row_seed + (unsigned int)tok);
-      const float u = ((float)h + 1.0f) * (1.0f / 4294967296.0f);
+      // exact in fp32, u in [2^-24, 1 - 2^-24]: the noise is always finite
+      // (same arithmetic as sampling.hip)
+      const float u = ((float)(h >> 9) + 0.5f) * (1.0f / 8388608.0f);
       s = lg * inv_temp - __logf(-__logf(u));
     }
     if (s == 0.0f) s = 0.0f;  // -0.0 ties with +0.0, as in argmax
