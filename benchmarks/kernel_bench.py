@@ -213,19 +213,27 @@ def bench_moe(results):
     GB/s is over the expert-weight bytes actually touched: the experts hit
     by this routing x 3*I*H bf16. For T <= 64 the fused path is also timed
     as a captured-graph replay; the eager loop reads per-expert row sets
-    back to the host (nonzero), so it cannot be captured at all."""
+    back to the host (nonzero), so it cannot be captured at all. The same
+    weights quantised to e4m3 give the fp8 rows: ops.moe_experts_fp8 fused at
+    both row blocks and its per-expert scaled_mm loop."""
     h, inter, e, k = 4096, 14336, 8, 2
     g = torch.Generator().manual_seed(0)
     w13 = (torch.randn(e, 2 * inter, h, generator=g) * h ** -0.5
            ).to(torch.bfloat16).cuda()
     w2 = (torch.randn(e, h, inter, generator=g) * inter ** -0.5
           ).to(torch.bfloat16).cuda()
-    for t in (1, 8, 64, 128, 256, 512, 2048):
+    # fp8 experts (csrc/moe_fp8.hip) on the same weights and routing; their
+    # GB/s counts one byte per weight
+    from clearml_serving_amd.models.quant import quantize_experts_fp8
+
+    f8 = quantize_experts_fp8(w13) + quantize_experts_fp8(w2)
+    for t in (1, 8, 32, 64, 128, 256, 512, 2048):
         x = torch.randn(t, h, generator=g).to(torch.bfloat16).cuda()
         ids, wts = ops.moe_route(torch.randn(t, e, generator=g).cuda(), k)
         hit = int(ids.unique().numel())
         bytes_moved = 2.0 * hit * 3 * inter * h
         shape = "t{}:experts_hit{}".format(t, hit)
+        x8, xs = ops.quant_fp8(x)
         cases = [
             ("moe_fused_bm16", lambda: ops.moe_experts(
                 x, w13, w2, ids, wts, block_m=16)),
@@ -233,6 +241,12 @@ def bench_moe(results):
                 x, w13, w2, ids, wts, block_m=64)),
             ("moe_eager_loop", lambda: ops._moe_experts_loop(
                 x, w13, w2, ids, wts)),
+            ("moe_fp8_fused_bm16", lambda: ops.moe_experts_fp8(
+                x8, xs, *f8, ids, wts, block_m=16)),
+            ("moe_fp8_fused_bm64", lambda: ops.moe_experts_fp8(
+                x8, xs, *f8, ids, wts, block_m=64)),
+            ("moe_fp8_loop", lambda: ops._moe_experts_fp8_loop(
+                x8, xs, *f8, ids, wts)),
         ]
         if t <= 64:
             for bm in (16, 64):
@@ -255,8 +269,9 @@ def bench_moe(results):
                     timeit(fn, iters=iters, warmup=5))
         for op, _fn in cases:
             dt = sorted(best[op])[1]
+            nbytes = bytes_moved / 2 if "fp8" in op else bytes_moved
             results.append(dict(op=op, shape=shape, us=dt * 1e6,
-                                gbps=bytes_moved / dt / 1e9))
+                                gbps=nbytes / dt / 1e9))
 
 
 BENCHES = {"attention": bench_attention, "decode": bench_decode,

@@ -777,11 +777,20 @@ class LlmEngine:
             raise ValueError(
                 "sliding_window={} is not supported for mixture-of-experts "
                 "models (num_experts={})".format(window, n_exp))
-        if cfg.quantization == "fp8":
+        if cfg.quantization == "fp8" and self.device.type != "cuda":
             raise ValueError(
-                "quantization='fp8' is not supported for mixture-of-experts "
-                "models (num_experts={}): the expert kernels are bf16".format(
-                    n_exp))
+                "quantization='fp8' for mixture-of-experts models "
+                "(num_experts={}) needs a GPU: the fp8 expert path is the "
+                "HIP kernels of ops/csrc/moe_fp8.hip".format(n_exp))
+        if cfg.quantization == "fp8" and base is not None:
+            # the fp8 kernels step K in 64-byte window pairs (bf16: 32)
+            dims = {k: int(cfg.overrides.get(k, getattr(base, k)))
+                    for k in ("hidden", "intermediate")}
+            if any(v % 64 for v in dims.values()):
+                raise ValueError(
+                    "quantization='fp8' for mixture-of-experts models needs "
+                    "hidden and intermediate to be multiples of 64, got "
+                    "{}".format(dims))
         if cfg.lora_modules:
             raise ValueError(
                 "lora_modules are not supported for mixture-of-experts "

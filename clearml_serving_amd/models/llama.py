@@ -206,6 +206,19 @@ class LlamaLayer(nn.Module):
         """norm -> gate_up -> silu*up -> down, WITHOUT the row-parallel
         all-reduce (see attn_half). ``lora``: attn_ctx["lora"] or None."""
         cfg = self.cfg
+        if cfg.num_experts > 0 and self.w13.dtype == torch.uint8:
+            # fp8 experts (models/quant.py): the norm emits the e4m3 row and
+            # its scale in one pass; the router runs on that row dequantised
+            # once in the model dtype, so routing sees what the experts see
+            x8, xs = ops.rmsnorm_fp8(attn_out, self.mlp_norm, cfg.rms_eps,
+                                     residual=residual)
+            dt = attn_out.dtype
+            x = x8.view(torch.float8_e4m3fn).to(dt) * xs.to(dt)[:, None]
+            ids, weights = ops.moe_route(self.router(x), cfg.experts_per_tok,
+                                         cfg.norm_topk_prob)
+            out = ops.moe_experts_fp8(x8, xs, self.w13, self.w13_scale,
+                                      self.w2, self.w2_scale, ids, weights)
+            return out if out.dtype == dt else out.to(dt)
         if cfg.num_experts > 0:
             # norm -> router -> routed experts; every launch is sync-free,
             # so the block captures into the decode graphs

@@ -138,11 +138,39 @@ class Fp8Linear(nn.Module):
         return out.reshape(*orig_shape[:-1], self.out_features)
 
 
+def quantize_experts_fp8(w: torch.Tensor):
+    """Expert stack [E, N, K] -> (e4m3 bytes uint8 [E, N, K], every row in
+    the ops.swizzle_fp8_weight layout, fp32 scales [E, N] = row absmax/448):
+    the operands of ops.moe_experts_fp8. One expert at a time, so the fp32
+    temporaries stay at one expert's size."""
+    e, n, k = w.shape
+    w8 = torch.empty(e, n, k, dtype=torch.uint8, device=w.device)
+    scale = torch.empty(e, n, dtype=torch.float32, device=w.device)
+    for i in range(e):
+        wf = w[i].float()
+        s = wf.abs().amax(dim=1, keepdim=True).clamp(min=1e-8) / F8_MAX
+        w8[i] = ops.swizzle_fp8_weight((wf / s).to(F8))
+        scale[i] = s.reshape(-1)
+    return w8, scale
+
+
 def quantize_llama_fp8(model: nn.Module) -> int:
     """Swap the projection Linears of a LlamaForCausalLM to Fp8Linear
-    (lm_head stays bf16 for logit fidelity). Returns layers converted."""
+    (lm_head stays bf16 for logit fidelity). A layer with experts also gets
+    its ``w13`` / ``w2`` stacks replaced by e4m3 buffers of the same names
+    plus ``w13_scale`` / ``w2_scale`` (quantize_experts_fp8); the bf16
+    parameters are dropped and the router stays in the model dtype. Returns
+    the number of projections and expert stacks converted."""
     n = 0
     for layer in getattr(model, "layers", []):
+        for name in ("w13", "w2"):
+            w = getattr(layer, name, None)
+            if isinstance(w, nn.Parameter):
+                w8, scale = quantize_experts_fp8(w.data)
+                delattr(layer, name)
+                layer.register_buffer(name, w8)
+                layer.register_buffer(name + "_scale", scale)
+                n += 1
         for name in ("qkv", "o_proj", "gate_up", "down"):
             lin = getattr(layer, name, None)
             if isinstance(lin, nn.Linear):

@@ -1000,6 +1000,156 @@ def _check_moe_shapes(x, w13, w2, ids) -> None:
             "got H={} I={} E={} k={}".format(MOE_MAX_EXPERTS, h, inter, e, k))
 
 
+# --------------------------------------------------------------------- #
+# Mixture of experts with fp8 (e4m3) expert weights (kernels:
+# csrc/moe_fp8.hip)
+# --------------------------------------------------------------------- #
+# Path threshold of moe_experts_fp8. It started at MOE_FUSED_MAX (128), which
+# was measured for bf16 experts; the fp8 table in profiles/moe_bench.txt puts
+# the fp8 crossover higher: fused (64-row block) 1177 us vs scaled_mm loop
+# 1628 us at T=256, 2071 vs 1641 us at T=512.
+MOE_FP8_FUSED_MAX = int(os.environ.get("CMLS_MOE_FP8_FUSED_MAX", "256"))
+# The row-block crossover measured where the bf16 one lies (same table: 469
+# vs 552 us at T=64, 784 vs 687 us at T=128), so MOE_BLOCK16_MAX serves both.
+
+
+def _dequant_fp8(q8: torch.Tensor, scale: torch.Tensor,
+                 swizzled: bool = False) -> torch.Tensor:
+    """e4m3 bytes [R, C] * per-row scale [R] -> fp32."""
+    if swizzled:
+        q8 = unswizzle_fp8_weight(q8)
+    return q8.view(torch.float8_e4m3fn).float() * scale.reshape(-1, 1)
+
+
+def _moe_experts_fp8_ref(x8, x_scale, w13_8, w13_scale, w2_8, w2_scale, ids,
+                         weights):
+    """fp32 per-expert loop over the dequantised operands; silu(g)*u is
+    rounded to bf16 and then quantised per row, as the fused path stores it."""
+    t, h = x8.shape
+    inter = w2_8.shape[2]
+    k = ids.shape[1]
+    xf = _dequant_fp8(x8, x_scale)
+    y = torch.zeros(t, k, h, dtype=torch.float32, device=x8.device)
+    for e in range(w13_8.shape[0]):
+        tok, choice = (ids == e).nonzero(as_tuple=True)
+        if tok.numel() == 0:
+            continue
+        gu = xf[tok] @ _dequant_fp8(w13_8[e], w13_scale[e], True).t()
+        act = torch.nn.functional.silu(gu[:, :inter]) * gu[:, inter:]
+        a8, a_scale = _quant_fp8_ref(act.to(torch.bfloat16))
+        y[tok, choice] = (_dequant_fp8(a8, a_scale)
+                          @ _dequant_fp8(w2_8[e], w2_scale[e], True).t())
+    out = torch.zeros(t, h, dtype=torch.float32, device=x8.device)
+    for j in range(k):  # ascending j, fp32, one rounding at the end
+        out += weights[:, j, None].float() * y[:, j]
+    return out.to(torch.bfloat16)
+
+
+def _scaled_mm_rows(a8, a_scale, w8, w_scale):
+    """(a8 * a_scale) @ (w8 * w_scale)^T -> bf16 through hipBLASLt, a8
+    [rows, K] with rows % 16 == 0 and w8 [N, K] in the SAME byte order along
+    K (here: both swizzled; a dot product does not see a common permutation
+    of K)."""
+    f8 = torch.float8_e4m3fn
+    return torch._scaled_mm(
+        a8.view(f8), w8.view(f8).t(), scale_a=a_scale.reshape(-1, 1),
+        scale_b=w_scale.reshape(1, -1), out_dtype=torch.bfloat16)
+
+
+def _moe_experts_fp8_loop(x8, x_scale, w13_8, w13_scale, w2_8, w2_scale, ids,
+                          weights):
+    """Prefill-sized GPU path: per-expert hipBLASLt scaled_mm on the single
+    swizzled copy of the expert weights. The gathered activation rows get the
+    same byte shuffle as the weight rows (swizzle_fp8_weight on [rows, K]),
+    which leaves every dot product unchanged, so no plain-layout copy of the
+    experts lives in HBM. Rows are padded to a multiple of 16 as in
+    Fp8Linear._gemm_q. Reads the row sets back to the host: not capturable.
+    Agrees with the fused path to fp8 tolerance, not bit for bit."""
+    t, h = x8.shape
+    inter = w2_8.shape[2]
+    k = ids.shape[1]
+    x8 = x8.view(torch.uint8)
+    y = torch.zeros(t, k, h, dtype=torch.float32, device=x8.device)
+    for e in range(w13_8.shape[0]):
+        tok, choice = (ids == e).nonzero(as_tuple=True)
+        rows = tok.numel()
+        if rows == 0:
+            continue
+        pad = (-rows) % 16
+        a8 = torch.nn.functional.pad(x8[tok], (0, 0, 0, pad))
+        a_scale = torch.nn.functional.pad(x_scale[tok], (0, pad), value=1.0)
+        gu = _scaled_mm_rows(swizzle_fp8_weight(a8), a_scale, w13_8[e],
+                             w13_scale[e])
+        g8, g_scale = silu_mul_fp8(gu[:, :inter], gu[:, inter:])
+        out_e = _scaled_mm_rows(swizzle_fp8_weight(g8), g_scale, w2_8[e],
+                                w2_scale[e])
+        y[tok, choice] = out_e[:rows].float()
+    out = torch.zeros(t, h, dtype=torch.float32, device=x8.device)
+    for j in range(k):
+        out += weights[:, j, None] * y[:, j]
+    return out.to(torch.bfloat16)
+
+
+def _check_moe_fp8_shapes(x8, w13_8, w2_8, ids) -> None:
+    """The fused fp8 kernel's shape contract, held on the loop path too."""
+    h, inter, e, k = x8.shape[1], w2_8.shape[2], w13_8.shape[0], ids.shape[1]
+    if h % 64 or inter % 64 or not (k <= e <= MOE_MAX_EXPERTS):
+        raise RuntimeError(
+            "moe_experts_fp8: need H % 64 == 0, I % 64 == 0 and k <= E <= {}, "
+            "got H={} I={} E={} k={}".format(MOE_MAX_EXPERTS, h, inter, e, k))
+
+
+def moe_experts_fp8(x8: torch.Tensor, x_scale: torch.Tensor,
+                    w13_8: torch.Tensor, w13_scale: torch.Tensor,
+                    w2_8: torch.Tensor, w2_scale: torch.Tensor,
+                    ids: torch.Tensor, weights: torch.Tensor,
+                    block_m: Optional[int] = None) -> torch.Tensor:
+    """moe_experts with e4m3 operands -> bf16 [T, H].
+
+    x8: e4m3 bytes [T, H] with fp32 row scales x_scale [T] (ops.rmsnorm_fp8 /
+    ops.quant_fp8). w13_8 [E, 2I, H] and w2_8 [E, H, I]: e4m3 bytes, every
+    row in the swizzle_fp8_weight layout, with fp32 scales per (expert,
+    output row): w13_scale [E, 2I], w2_scale [E, H]
+    (models/quant.py quantize_experts_fp8). ids, weights as in moe_experts.
+
+    Reference semantics (CPU path): every operand dequantised to fp32, the
+    per-expert loop of moe_experts, with silu(g)*u rounded to bf16 and then
+    quantised per row (_quant_fp8_ref) before the down projection; the sum
+    over j in fp32 in ascending j, one final rounding.
+
+    GPU: H % 64 == 0, I % 64 == 0, k <= E <= 64, contiguous 16-byte-aligned
+    operands, else RuntimeError. A call with T <= MOE_FP8_FUSED_MAX, and
+    every call under graph capture, runs the fused path (csrc/moe_fp8.hip:
+    align, grouped fp8 gate/up GEMM, row quantisation, grouped fp8 down
+    GEMM, combine; sync-free), with row block 16 up to MOE_BLOCK16_MAX
+    tokens and 64 above; ``block_m`` forces the fused path and its row block.
+    Both thresholds started from the values measured for the bf16 experts;
+    the fp8 table in profiles/moe_bench.txt confirmed the row-block one and
+    moved the path one from 128 to 256. Larger eager calls run a per-expert
+    torch._scaled_mm loop on the same swizzled weights.
+
+    Bit-reproducibility, batch invariance and row-block independence hold
+    within the fused path, as for moe_experts; the loop agrees with it to
+    fp8 tolerance only. PRECONDITION: ids in [0, E), as for moe_experts.
+    """
+    if x8.is_cuda:
+        ext = _require_ext("moe_experts_fp8")
+        if ext is not None:
+            t = x8.shape[0]
+            if block_m is None:
+                if (t > MOE_FP8_FUSED_MAX
+                        and not torch.cuda.is_current_stream_capturing()):
+                    _check_moe_fp8_shapes(x8, w13_8, w2_8, ids)
+                    return _moe_experts_fp8_loop(
+                        x8, x_scale, w13_8, w13_scale, w2_8, w2_scale, ids,
+                        weights)
+                block_m = 16 if t <= MOE_BLOCK16_MAX else 64
+            return ext.moe_experts_fp8(x8, x_scale, w13_8, w13_scale, w2_8,
+                                       w2_scale, ids, weights, int(block_m))
+    return _moe_experts_fp8_ref(x8, x_scale, w13_8, w13_scale, w2_8,
+                                w2_scale, ids, weights)
+
+
 def moe_ffn(x: torch.Tensor, router_weight: torch.Tensor, w13: torch.Tensor,
             w2: torch.Tensor, top_k: int,
             renormalize: bool = True) -> torch.Tensor:

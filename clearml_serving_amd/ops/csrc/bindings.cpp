@@ -66,6 +66,11 @@ std::vector<torch::Tensor> moe_align(torch::Tensor ids, int64_t num_experts,
 torch::Tensor moe_experts(torch::Tensor x, torch::Tensor w13, torch::Tensor w2,
                           torch::Tensor ids, torch::Tensor weights,
                           int64_t block_m);
+torch::Tensor moe_experts_fp8(torch::Tensor x8, torch::Tensor x_scale,
+                              torch::Tensor w13_8, torch::Tensor w13_scale,
+                              torch::Tensor w2_8, torch::Tensor w2_scale,
+                              torch::Tensor ids, torch::Tensor weights,
+                              int64_t block_m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "clearml-serving-amd gfx950 kernel library";
@@ -126,4 +131,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_experts", &moe_experts, py::arg("x"), py::arg("w13"),
         py::arg("w2"), py::arg("ids"), py::arg("weights"),
         py::arg("block_m") = 16);
+  m.def("moe_experts_fp8", &moe_experts_fp8, py::arg("x8"),
+        py::arg("x_scale"), py::arg("w13_8"), py::arg("w13_scale"),
+        py::arg("w2_8"), py::arg("w2_scale"), py::arg("ids"),
+        py::arg("weights"), py::arg("block_m") = 16);
 }

@@ -21,7 +21,7 @@
 // with 16-byte lane loads straight from global and a deterministic LDS
 // reduce. Expert weights stream once per row block; the gathered A rows are
 // re-read by every column workgroup and ride in L2.
-#include "common.h"
+#include "moe.h"
 
 namespace {
 
@@ -31,8 +31,8 @@ typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 #define MFMA16(A, B, C) \
   __builtin_amdgcn_mfma_f32_16x16x32_bf16((A), (B), (C), 0, 0, 0)
 
-constexpr int MOE_MAX_E = 64;    // one lane per expert in moe_route
-constexpr int MOE_MAX_K = 8;
+constexpr int MOE_MAX_E = cmls_moe::MAX_E;  // one lane per expert in moe_route
+constexpr int MOE_MAX_K = cmls_moe::MAX_K;
 constexpr int NT = 16;           // weight columns per workgroup
 constexpr int NW = 8;            // waves (split K)
 constexpr int KSTEP = 32;
@@ -310,9 +310,18 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(
   *reinterpret_cast<uint32x2*>(out + (long)t * H + c) = o.u;
 }
 
+void check_aligned16(const torch::Tensor& v, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0, "moe: ",
+              name, " must be 16-byte aligned");
+}
+
 long moe_nb_max(long s, long e, long block_m) {
   return (s + std::min(e, s) * (block_m - 1)) / block_m;
 }
+
+}  // namespace
+
+namespace cmls_moe {  // shared with moe_fp8.hip (moe.h)
 
 void check_ids(const torch::Tensor& ids, const char* op) {
   TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kInt &&
@@ -322,11 +331,6 @@ void check_ids(const torch::Tensor& ids, const char* op) {
                   ids.size(1) <= MOE_MAX_K,
               op, ": need T >= 1 and 1 <= k <= ", MOE_MAX_K);
   TORCH_CHECK(ids.numel() <= INT_MAX / 2, op, ": T * k too large");
-}
-
-void check_aligned16(const torch::Tensor& v, const char* name) {
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0, "moe: ",
-              name, " must be 16-byte aligned");
 }
 
 void launch_align(const torch::Tensor& ids, long n_exp, long block_m,
@@ -343,7 +347,21 @@ void launch_align(const torch::Tensor& ids, long n_exp, long block_m,
                      (int)block_m, (int)nb_max);
 }
 
-}  // namespace
+void launch_combine(const torch::Tensor& y, const torch::Tensor& weights,
+                    torch::Tensor& out, const char* op) {
+  const long t = out.size(0), h = out.size(1), k = weights.size(1);
+  const long cblk = (h / 4 + 255) / 256;
+  TORCH_CHECK(t <= INT_MAX && cblk <= 65535, op, ": shape too large");
+  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)t, (unsigned)cblk),
+                     dim3(256), 0, cmls::current_stream(),
+                     y.data_ptr<float>(), weights.data_ptr<float>(),
+                     (__hip_bfloat16*)out.data_ptr(), (int)k, (int)h);
+}
+
+}  // namespace cmls_moe
+
+using cmls_moe::check_ids;
+using cmls_moe::launch_align;
 
 std::vector<torch::Tensor> moe_route(torch::Tensor logits, int64_t top_k,
                                      bool renormalize) {
@@ -457,11 +475,6 @@ torch::Tensor moe_experts(torch::Tensor x, torch::Tensor w13, torch::Tensor w2,
     LAUNCH_MOE(4, false, act, w2, y, h, inter);
   }
 #undef LAUNCH_MOE
-  const long cblk = (h / 4 + 255) / 256;
-  TORCH_CHECK(t <= INT_MAX && cblk <= 65535, "moe_experts: shape too large");
-  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)t, (unsigned)cblk),
-                     dim3(256), 0, stream_, y.data_ptr<float>(),
-                     weights.data_ptr<float>(),
-                     (__hip_bfloat16*)out.data_ptr(), (int)k, (int)h);
+  cmls_moe::launch_combine(y, weights, out, "moe_experts");
   return out;
 }
