@@ -274,10 +274,95 @@ def bench_moe(results):
                                 gbps=nbytes / dt / 1e9))
 
 
+def bench_sample_rows(results):
+    """Fused per-row sampler and penalties (csrc/sample_rows.hip), bf16
+    logits, V = 128256, old and new paths alternated in one process (median
+    of three): top-k 50 / top-p 0.9 on every row against the library
+    composition of sample_top_k_top_p; plain rows against
+    sample_token_bitmask at slot -1; apply_penalties with 512 entries per
+    row against clone + per-row index updates. "filters_off" passes the
+    filter tensors with every row's filter off (the select kernel launches
+    and leaves at once), which is what plain rows pay inside a mixed engine
+    batch. At B = 64 the batch is also run with 64 distinct (top_k, top_p)
+    settings: 64 grouped calls with a copy back each, as the engine's
+    grouped path issues them, against one sample_rows call and one copy.
+    GB/s (logits read once) is given for the plain single-pass rows only."""
+    v, ext = 128256, ops.extension_or_none()
+    bank = torch.zeros(1, (v + 31) // 32, dtype=torch.int32, device="cuda")
+    for b in (1, 8, 64):
+        logits = (torch.randn(b, v, device="cuda") * 3).to(torch.bfloat16)
+        temp = torch.full((b,), 0.8, device="cuda")
+        seed = torch.arange(b, device="cuda", dtype=torch.int32)
+        k = torch.full((b,), 50, device="cuda", dtype=torch.int32)
+        p = torch.full((b,), 0.9, device="cuda")
+        k_off, p_off, m_off = k * 0, p * 0 + 1, p * 0
+        slot = torch.full((b,), -1, device="cuda", dtype=torch.int32)
+        n = 512
+        tok = torch.stack([torch.randperm(v, device="cuda")[:n]
+                           for _ in range(b)]).to(torch.int32)
+        cnt = torch.randint(0, 3, (b * n,), device="cuda", dtype=torch.int32)
+        flags = torch.zeros(b * n, device="cuda", dtype=torch.int32)
+        offs = torch.arange(b + 1, device="cuda", dtype=torch.int32) * n
+        pres = torch.full((b,), 0.5, device="cuda")
+        freq = torch.full((b,), 0.2, device="cuda")
+        rep = torch.full((b,), 1.2, device="cuda")
+
+        def penalties_eager():
+            out = logits.clone()
+            for r in range(b):
+                idx = tok[r].long()
+                c = cnt[r * n:(r + 1) * n].float()
+                x = out[r, idx].float()
+                x = torch.where(x > 0, x / 1.2, x * 1.2) - 0.2 * c
+                out[r, idx] = (x - 0.5 * (c > 0)).to(out.dtype)
+            return out
+
+        cases = [
+            ("sampler_k50_p0.9_library", lambda: ext.sample_top_k_top_p(
+                logits, 0.8, 50, 0.9, 7)),
+            ("sampler_k50_p0.9_sample_rows", lambda: ops.sample_rows(
+                logits, temp, k, p, None, seed)),
+            ("sampler_plain_token_bitmask", lambda: ops.sample_token_bitmask(
+                logits, bank, slot, temp, seed)),
+            ("sampler_plain_sample_rows", lambda: ops.sample_rows(
+                logits, temp, None, None, None, seed)),
+            ("sampler_plain_filters_off", lambda: ops.sample_rows(
+                logits, temp, k_off, p_off, m_off, seed)),
+            ("penalties_eager_rows", penalties_eager),
+            ("penalties_apply_penalties", lambda: ops.apply_penalties(
+                logits, tok.view(-1), cnt, flags, offs, pres, freq, rep)),
+        ]
+        if b == 64:
+            ks = [20 + r for r in range(b)]
+            ps = [0.5 + 0.007 * r for r in range(b)]
+            kd = torch.tensor(ks, device="cuda", dtype=torch.int32)
+            pd = torch.tensor(ps, device="cuda")
+            cases += [
+                ("sampler_64_settings_grouped", lambda: [
+                    ext.sample_top_k_top_p(logits[[r]], 0.8, ks[r], ps[r],
+                                           7).cpu() for r in range(b)]),
+                ("sampler_64_settings_sample_rows", lambda: ops.sample_rows(
+                    logits, temp, kd, pd, None, seed).cpu()),
+            ]
+        runs = {}
+        for _ in range(3):
+            for op, fn in cases:
+                runs.setdefault(op, []).append(timeit(fn, iters=100,
+                                                      warmup=10))
+        for op, _fn in cases:
+            lo, dt, hi = sorted(runs[op])
+            r = dict(op=op, shape="{}x{} [{:.1f}-{:.1f}us]".format(
+                b, v, lo * 1e6, hi * 1e6), us=dt * 1e6)
+            if op.startswith("sampler_plain"):
+                r["gbps"] = logits.numel() * 2 / dt / 1e9
+            results.append(r)
+
+
 BENCHES = {"attention": bench_attention, "decode": bench_decode,
            "memops": bench_memops, "gemm": bench_gemm,
            "sampling": bench_sampling, "lora": bench_lora,
-           "guided": bench_guided, "moe": bench_moe}
+           "guided": bench_guided, "moe": bench_moe,
+           "sample_rows": bench_sample_rows}
 
 
 def main():
@@ -293,8 +378,8 @@ def main():
             fn(results)
     for r in results:
         perf = ("{:8.1f} TF".format(r["tflops"]) if "tflops" in r
-                else "{:8.1f} GB/s".format(r["gbps"]))
-        print("{:28s} {:22s} {:9.1f} us {}".format(
+                else "{:8.1f} GB/s".format(r["gbps"]) if "gbps" in r else "")
+        print("{:32s} {:30s} {:9.1f} us {}".format(
             r["op"], r["shape"], r["us"], perf))
     if args.out:
         with open(args.out, "wt") as f:

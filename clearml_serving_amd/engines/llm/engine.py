@@ -31,12 +31,13 @@ KV sizing: pages are allocated once at startup from a fraction of free HBM
 
 import asyncio
 import json
+import math
 import os
 import random
 import threading
 import time
 import uuid
-from collections import OrderedDict, deque
+from collections import Counter, OrderedDict, deque
 from dataclasses import dataclass, field
 from typing import Any, AsyncGenerator, Dict, List, Optional
 
@@ -101,12 +102,22 @@ class HfTokenizer:
         return self._tok.decode(ids)
 
 
+# Largest batch whose plain rows (no top-k / top-p / min-p on any row) stay
+# on ops.sample_rows; larger ones take sample_token_bitmask at slot -1, which
+# draws the same token. MI355X, bf16, V = 128256 (profiles/sampler_bench.txt):
+# sample_rows 11.2 / 11.3 us against 11.6 / 11.8 us at B = 1 / 8, but 18.6
+# [18.6-19.1] against 18.1 [18.0-18.1] us at B = 64. Between 8 and 64 rows
+# nothing was measured, so only the measured wins stay.
+FUSED_PLAIN_MAX_ROWS = 8
+
+
 # --------------------------------------------------------------------- #
 @dataclass
 class SamplingParams:
     temperature: float = 1.0
     top_k: int = 0
     top_p: float = 1.0
+    min_p: float = 0.0                   # keep tokens with P >= min_p * P_max
     max_tokens: int = 128
     stop_token_ids: List[int] = field(default_factory=list)
     stop: List[str] = field(default_factory=list)
@@ -139,6 +150,7 @@ class SamplingParams:
             top_k = int(body.get("top_k", 0) or 0)
             # max_completion_tokens: the newer OpenAI name for max_tokens
             top_p = float(body.get("top_p", 1.0))
+            min_p = float(body.get("min_p", 0.0) or 0.0)
             mt = body.get("max_tokens")
             if mt is None:
                 mt = body.get("max_completion_tokens")
@@ -154,7 +166,7 @@ class SamplingParams:
             seed = int(seed) if seed is not None else None
         except (TypeError, ValueError, OverflowError):
             raise ValueError("sampling parameters must be numeric "
-                             "(temperature/top_k/top_p/max_tokens/"
+                             "(temperature/top_k/top_p/min_p/max_tokens/"
                              "penalties/seed)")
         import math as _math
 
@@ -167,6 +179,8 @@ class SamplingParams:
                              .format(top_k))
         if not (0.0 < top_p <= 1.0):
             raise ValueError("top_p must be in (0, 1], got {}".format(top_p))
+        if not (0.0 <= min_p <= 1.0):
+            raise ValueError("min_p must be in [0, 1], got {}".format(min_p))
         if max_tokens < 1:
             raise ValueError("max_tokens must be >= 1, got {}".format(
                 max_tokens))
@@ -252,6 +266,7 @@ class SamplingParams:
             temperature=temperature,
             top_k=top_k,
             top_p=top_p,
+            min_p=min_p,
             max_tokens=max_tokens,
             stop_token_ids=stop_ids,
             stop=[s for s in stop if s],
@@ -505,6 +520,10 @@ class Sequence:
         self.cache_salt = cache_salt
         self.prompt_ids = prompt_ids
         self.output_ids: List[int] = []
+        # penalty state, maintained where tokens are emitted or folded into
+        # the prompt: Counter(output_ids) and set(prompt_ids)
+        self.output_counts: Counter = Counter()
+        self.prompt_set = set(prompt_ids)
         self.generated = 0  # survives preemption (output folds into prompt)
         self.prefilled = 0  # prompt tokens already in the KV cache
         self.params = params
@@ -932,6 +951,10 @@ class LlmEngine:
             # penalties need; fail loudly instead of silently ignoring
             raise ValueError(
                 "presence/frequency/repetition penalties are not supported "
+                "under tensor parallelism yet")
+        if params.min_p > 0.0 and getattr(self, "tp_size", 1) > 1:
+            raise ValueError(
+                "min_p needs the full-vocab maximum and is not supported "
                 "under tensor parallelism yet")
         if params.logprobs is not None and getattr(self, "tp_size", 1) > 1:
             raise ValueError(
@@ -1498,6 +1521,8 @@ class LlmEngine:
         self._free_blocks(victim)
         victim.prompt_ids = victim.prompt_ids + victim.output_ids
         victim.output_ids = []
+        victim.prompt_set.update(victim.output_counts)
+        victim.output_counts.clear()
         self.waiting.insert(0, victim)
         self.stats["preemptions"] = self.stats.get("preemptions", 0) + 1
         return True
@@ -2083,20 +2108,120 @@ class LlmEngine:
             logits, next_ids = self._sample_grouped(seqs, logits)
         self._emit_sampled(seqs, next_ids, logits)
 
+    _no_mask: Optional[torch.Tensor] = None  # [1, W] bank for slot -1
+
+    def _penalty_entries(self, seqs: List[Sequence], vocab: int):
+        """CSR penalty entries of a step, or None when no row needs any:
+        (tok, cnt, flags, offsets, presence, frequency, repetition) as host
+        lists, tokens unique within a row. cnt is the output count (kept at
+        0 when the row has neither presence nor frequency penalty), flag
+        bit 0 the min_tokens ban."""
+        tok: List[int] = []
+        cnt: List[int] = []
+        flags: List[int] = []
+        offsets = [0]
+        pres, freq, rep = [], [], []
+        for s in seqs:
+            p = s.params
+            ban = set()
+            if p.min_tokens > s.generated:
+                ban = set(p.stop_token_ids)
+                if not p.ignore_eos:
+                    ban.add(self.tokenizer.eos_id)
+            counted = bool(p.presence_penalty or p.frequency_penalty)
+            row: Dict[int, int] = {}
+            if p.repetition_penalty != 1.0:
+                row = dict.fromkeys(s.prompt_set, 0)
+            if counted or p.repetition_penalty != 1.0:
+                for t, c in s.output_counts.items():
+                    row[t] = c if counted else 0
+            for t in ban:
+                row.setdefault(t, 0)
+            for t, c in row.items():
+                if 0 <= t < vocab:
+                    tok.append(t)
+                    cnt.append(c)
+                    flags.append(1 if t in ban else 0)
+            offsets.append(len(tok))
+            pres.append(p.presence_penalty)
+            freq.append(p.frequency_penalty)
+            rep.append(p.repetition_penalty)
+        return (tok, cnt, flags, offsets, pres, freq, rep) if tok else None
+
+    def _sample_fused(self, seqs: List[Sequence], logits: torch.Tensor):
+        """GPU logits, TP = 1: one apply_penalties launch if any row needs
+        it, one sample_rows call for the whole heterogeneous batch, one
+        copy back; the step's host arrays travel in two pinned staging
+        copies (one int32, one float32). A seeded row's token depends on
+        its own logits and parameters only, not on its batch neighbours."""
+        dev = logits.device
+
+        def stage(lists, dtype):
+            flat = torch.tensor([v for part in lists for v in part],
+                                dtype=dtype).pin_memory()
+            return flat.to(dev, non_blocking=True).split(
+                [len(part) for part in lists])
+
+        n = len(seqs)
+        params = [s.params for s in seqs]
+        draws = torch.randint(0, 2**31 - 1, (n,)).tolist()
+        seeds = [(p.seed + s.generated) & 0x7FFFFFFF
+                 if p.seed is not None else draws[i]
+                 for i, (s, p) in enumerate(zip(seqs, params))]
+        tok, cnt, flags, offsets, pres, freq, rep = \
+            self._penalty_entries(seqs, logits.shape[-1]) or [[]] * 7
+        seed, top_k, slot, tok, cnt, flags, offsets = stage(
+            [seeds, [p.top_k for p in params], [-1] * n, tok, cnt, flags,
+             offsets], torch.int32)
+        temp, top_p, min_p, pres, freq, rep = stage(
+            [[p.temperature for p in params], [p.top_p for p in params],
+             [p.min_p for p in params], pres, freq, rep], torch.float32)
+        if len(offsets):
+            logits = ops.apply_penalties(logits, tok, cnt, flags, offsets,
+                                         pres, freq, rep)
+        filtered = any(p.top_k > 0 or p.top_p < 1.0 or p.min_p > 0.0
+                       for p in params)
+        if not filtered and n > FUSED_PLAIN_MAX_ROWS:
+            # same draw, same seeds: the masked sampler with no mask
+            words = (logits.shape[-1] + 31) // 32
+            if self._no_mask is None or self._no_mask.shape[1] != words:
+                self._no_mask = torch.zeros(1, words, dtype=torch.int32,
+                                            device=dev)
+            next_ids = ops.sample_token_bitmask(logits, self._no_mask, slot,
+                                                temp, seed)
+        elif filtered:
+            next_ids = ops.sample_rows(logits, temp, top_k, top_p, min_p,
+                                       seed)
+        else:
+            next_ids = ops.sample_rows(logits, temp, None, None, None, seed)
+        # a row with nothing finite draws -1; the grouped path returns
+        # token 0 for such a row
+        return logits, next_ids.cpu().clamp_(min=0)
+
     def _sample_grouped(self, seqs: List[Sequence], logits: torch.Tensor):
-        """Penalties, then one sampler launch per group of rows with
-        identical sampling params -> (post-penalty logits, next ids)."""
+        """Penalties and sampling -> (post-penalty logits, next ids). GPU
+        logits take the fused per-row path (CMLS_FUSED_SAMPLER=0 restores
+        the grouped one); CPU logits run one sampler call per group of rows
+        with identical sampling params."""
+        if logits.is_cuda and os.environ.get("CMLS_FUSED_SAMPLER",
+                                             "1") != "0":
+            return self._sample_fused(seqs, logits)
         logits = self._apply_penalties(logits, seqs)
         # group rows by identical sampling params for batched kernels
         # (a request-level seed gets its own group + generator)
         groups: Dict[tuple, List[int]] = {}
         for i, s in enumerate(seqs):
             key = (s.params.temperature, s.params.top_k, s.params.top_p,
-                   s.params.seed)
+                   s.params.seed, s.params.min_p)
             groups.setdefault(key, []).append(i)
         next_ids = torch.empty(len(seqs), dtype=torch.long)
-        for (temp, top_k, top_p, seed), idxs in groups.items():
+        for (temp, top_k, top_p, seed, min_p), idxs in groups.items():
             rows = logits[idxs] if len(idxs) < len(seqs) else logits
+            if min_p > 0.0 and temp != 0.0:
+                rf = rows.float()
+                floor = rf.max(-1, keepdim=True).values \
+                    + temp * math.log(min_p)
+                rows = rows.masked_fill(rf < floor, float("-inf"))
             gen = None
             if seed is not None and temp != 0.0:
                 s0 = seqs[idxs[0]]
@@ -2111,7 +2236,7 @@ class LlmEngine:
     def _sample_guided(self, seqs: List[Sequence],
                        logits: torch.Tensor) -> None:
         """A step with at least one guided row (TP=1). Plain rows (no
-        top-k/top-p, penalties, logprobs or min_tokens ban) -- guided or
+        top-k/top-p/min-p, penalties, logprobs or min_tokens ban) -- guided or
         not -- go through ONE fused mask+draw launch with per-row
         temperature and seed; the others are masked out of place and then
         take the usual penalties -> grouped sampler -> logprobs flow, so
@@ -2132,8 +2257,9 @@ class LlmEngine:
             p = s.params
             if slots[i] == -2:
                 self._finish_dead_end(s)
-            elif (p.top_k > 0 or p.top_p < 1.0 or p.has_penalties()
-                  or p.logprobs is not None or p.min_tokens > s.generated):
+            elif (p.top_k > 0 or p.top_p < 1.0 or p.min_p > 0.0
+                  or p.has_penalties() or p.logprobs is not None
+                  or p.min_tokens > s.generated):
                 rest.append(i)
             else:
                 fused.append(i)
@@ -2219,6 +2345,7 @@ class LlmEngine:
             if s.finished:
                 break
             s.output_ids.append(tok)
+            s.output_counts[tok] += 1
             s.generated += 1
             if s.first_token_time is None:
                 s.first_token_time = now

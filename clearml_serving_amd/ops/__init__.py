@@ -793,6 +793,147 @@ def sample_token_bitmask(logits: torch.Tensor, bank: torch.Tensor,
 
 
 # --------------------------------------------------------------------- #
+# Fused per-row sampler and penalties (kernels: csrc/sample_rows.hip). The
+# plain-PyTorch paths below DEFINE the semantics the kernels are tested
+# against.
+# --------------------------------------------------------------------- #
+def _pcg_hash(x: torch.Tensor) -> torch.Tensor:
+    """The kernels' 32-bit pcg hash on an int64 tensor holding uint32s."""
+    m = 0xFFFFFFFF
+    x = (x * 747796405 + 2891336453) & m
+    w = (((x >> ((x >> 28) + 4)) ^ x) * 277803737) & m
+    return (w >> 22) ^ w
+
+
+def _row_threshold(x: torch.Tensor, t: float, k: int, p: float,
+                   mp: float) -> float:
+    """tau of one float64 row (NaN already excluded by the caller's mask)."""
+    live = x[~torch.isnan(x)]
+    x_max = float(live.max())
+    vals, counts = torch.unique(live, return_counts=True)  # ascending
+    vals, counts = vals.flip(0), counts.flip(0)
+    mass = torch.where(vals == x_max, torch.ones_like(vals),
+                       torch.exp((vals - x_max) / t)) * counts
+    cum = mass.cumsum(0)                                   # M(v)
+    tau_k, m_k = float("-inf"), float(cum[-1])
+    if 0 < k < x.numel() and k <= int(counts.sum()):
+        i = int(torch.searchsorted(counts.cumsum(0), k))
+        tau_k, m_k = float(vals[i]), float(cum[i])
+    tau = tau_k
+    if p < 1.0:
+        ok = (vals >= tau_k) & (cum <= p * m_k)
+        tau = max(tau, float(vals[ok].min()) if bool(ok.any()) else x_max)
+    if mp > 0.0:
+        tau = max(tau, x_max + t * math.log(mp))
+    return tau
+
+
+def sample_rows(logits: torch.Tensor, temperature: torch.Tensor,
+                top_k: Optional[torch.Tensor], top_p: Optional[torch.Tensor],
+                min_p: Optional[torch.Tensor],
+                seed: torch.Tensor) -> torch.Tensor:
+    """One token per row of a heterogeneous batch -> int64 [B].
+
+    logits [B, V] bf16/fp16/fp32 (row-strided views accepted); temperature
+    f32 [B], top_k i32 [B], top_p f32 [B], min_p f32 [B], seed i32 [B]. A
+    filter given as None is off for every row and costs nothing.
+
+    Per row: NaN logits never win and carry no probability mass, -inf logits
+    are never kept, a row with nothing finite returns -1; a +inf logit is the
+    maximum and holds all the mass. temperature == 0 is
+    greedy (argmax, lowest index on ties; filters ignored). Otherwise every
+    filter is a value threshold and the kept set is {t : x_t >= tau}, tau =
+    max(tau_k, tau_p, tau_m), with P = softmax(x / T) over the non-NaN
+    tokens and M(v) = sum of P_t over x_t >= v:
+      tau_k  the k-th largest value (top_k <= 0 or >= V: off); ties at the
+             k-th value are all kept
+      tau_p  the lowest value v >= tau_k with M(v) <= top_p * M(tau_k), the
+             row maximum if there is none (top_p >= 1: off)
+      tau_m  x_max + T * ln(min_p) (min_p <= 0: off)
+    Top-p tie rule: without a tie at the cut this is "sort, drop the tokens
+    whose inclusive cumulative probability exceeds p"; with one, the whole
+    group of equal logits is kept or dropped together, so the result never
+    depends on token index.
+
+    The draw is sample_token_bitmask's: argmax of x / T - log(-log u) with
+    u = ((pcg(pcg(seed) + token) >> 9) + 0.5) * 2^-23, lowest token on
+    ties. A row's token depends on its logits and its five parameters only,
+    not on its position, the batch or the vocabulary split. This CPU path
+    lifts the row to float64; the kernels work in fp32."""
+    if logits.is_cuda:
+        ext = _require_ext("sample_rows")
+        if ext is not None:
+            return ext.sample_rows(logits, temperature, top_k, top_p, min_p,
+                                   seed)
+    rows, vocab = logits.shape
+    out = torch.full((rows,), -1, dtype=torch.long, device=logits.device)
+    dev = logits.device
+    tokens = torch.arange(vocab, dtype=torch.int64, device=dev)
+    for r in range(rows):
+        x = logits[r].double()
+        keep = ~torch.isnan(x) & (x > float("-inf"))
+        if not bool(keep.any()):
+            continue
+        t = float(temperature[r])
+        if t <= 0.0:
+            score = x
+        else:
+            k = int(top_k[r]) if top_k is not None else 0
+            p = float(top_p[r]) if top_p is not None else 1.0
+            mp = float(min_p[r]) if min_p is not None else 0.0
+            if 0 < k < vocab or p < 1.0 or mp > 0.0:
+                keep &= x >= _row_threshold(x, t, k, p, mp)
+            row_seed = _pcg_hash(torch.tensor(int(seed[r]) & 0xFFFFFFFF,
+                                              device=dev))
+            h = _pcg_hash((row_seed + tokens) & 0xFFFFFFFF)
+            u = ((h >> 9).float() + 0.5) * (1.0 / 8388608.0)
+            inv_t = float(torch.tensor(1.0) / torch.tensor(t))
+            score = x * inv_t - torch.log(-torch.log(u.double()))
+        score = torch.where(keep, score, torch.full_like(score, -math.inf))
+        if bool((score > -math.inf).any()):
+            out[r] = int(score.argmax())  # first maximum = lowest token
+    return out
+
+
+def apply_penalties(logits: torch.Tensor, tok: torch.Tensor,
+                    cnt: torch.Tensor, flags: torch.Tensor,
+                    offsets: torch.Tensor, presence: torch.Tensor,
+                    frequency: torch.Tensor,
+                    repetition: torch.Tensor) -> torch.Tensor:
+    """New [B, V] tensor: ``logits`` with per-entry penalties applied; the
+    source is never written (decode-graph logits are replay buffers).
+
+    Entries offsets[r]..offsets[r+1] of tok/cnt/flags (int32 [N]; offsets
+    int32 [B+1]) belong to row r. PRECONDITIONS: offsets is non-decreasing
+    from 0, and tokens are unique within a row (the GPU scatter is then
+    race-free without atomics). Per entry, in
+    fp32: x = x / repetition[r] if x > 0 else x * repetition[r]; x -=
+    frequency[r] * cnt; x -= presence[r] if cnt > 0; flag bit 0 sets x to
+    -inf. cnt is the token's count in the output (0 = prompt only). The
+    result rounds once to the logits dtype; every element without an entry
+    is bit-identical, and an entry with tok outside [0, V) is skipped."""
+    if logits.is_cuda:
+        ext = _require_ext("apply_penalties")
+        if ext is not None:
+            return ext.apply_penalties(logits, tok, cnt, flags, offsets,
+                                       presence, frequency, repetition)
+    out = logits.clone()
+    vocab = logits.shape[1]
+    for r in range(logits.shape[0]):
+        lo, hi = int(offsets[r]), int(offsets[r + 1])
+        t = tok[lo:hi].long()
+        ok = (t >= 0) & (t < vocab)
+        t, c, f = t[ok], cnt[lo:hi][ok], flags[lo:hi][ok]
+        x = out[r, t].float()
+        x = torch.where(x > 0, x / repetition[r], x * repetition[r])
+        x = x - frequency[r] * c.float()
+        x = x - presence[r] * (c > 0).float()
+        x = torch.where((f & 1) != 0, torch.full_like(x, -math.inf), x)
+        out[r, t] = x.to(out.dtype)
+    return out
+
+
+# --------------------------------------------------------------------- #
 # Mixture of experts (kernels: csrc/moe.hip). The plain-PyTorch references
 # below DEFINE the semantics the kernels are tested against.
 # --------------------------------------------------------------------- #

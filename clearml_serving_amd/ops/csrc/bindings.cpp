@@ -59,6 +59,16 @@ torch::Tensor sample_token_bitmask(torch::Tensor logits, torch::Tensor bank,
                                    torch::Tensor slot,
                                    torch::Tensor temperature,
                                    torch::Tensor seed);
+torch::Tensor sample_rows(torch::Tensor logits, torch::Tensor temperature,
+                          c10::optional<torch::Tensor> top_k,
+                          c10::optional<torch::Tensor> top_p,
+                          c10::optional<torch::Tensor> min_p,
+                          torch::Tensor seed);
+torch::Tensor apply_penalties(torch::Tensor logits, torch::Tensor tok,
+                              torch::Tensor cnt, torch::Tensor flags,
+                              torch::Tensor offsets, torch::Tensor presence,
+                              torch::Tensor frequency,
+                              torch::Tensor repetition);
 std::vector<torch::Tensor> moe_route(torch::Tensor logits, int64_t top_k,
                                      bool renormalize);
 std::vector<torch::Tensor> moe_align(torch::Tensor ids, int64_t num_experts,
@@ -124,6 +134,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_token_bitmask", &sample_token_bitmask, py::arg("logits"),
         py::arg("bank"), py::arg("slot"), py::arg("temperature"),
         py::arg("seed"));
+  m.def("sample_rows", &sample_rows, py::arg("logits"),
+        py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
+        py::arg("min_p"), py::arg("seed"));
+  m.def("apply_penalties", &apply_penalties, py::arg("logits"),
+        py::arg("tok"), py::arg("cnt"), py::arg("flags"), py::arg("offsets"),
+        py::arg("presence"), py::arg("frequency"), py::arg("repetition"));
   m.def("moe_route", &moe_route, py::arg("logits"), py::arg("top_k"),
         py::arg("renormalize") = true);
   m.def("moe_align", &moe_align, py::arg("ids"), py::arg("num_experts"),
