@@ -358,11 +358,75 @@ def bench_sample_rows(results):
             results.append(r)
 
 
+def bench_qk_rope_kv(results):
+    """Fused norm-less ops.qk_rope_kv (csrc/qk_rope_kv.hip) against the
+    rope_inplace + kv_cache_write pair it stands in for, Llama-3-8B head
+    shapes (32 / 8 heads, D = 128), bf16 and fp8 caches, q/k/v as views of
+    the merged QKV output. Each side is a captured graph of 16 repetitions
+    (the ops live inside decode graphs; an eager A/B would mostly time two
+    launches against one), the two graphs are replayed alternately and the
+    median of three rounds is kept. us is per repetition; GB/s counts the
+    bytes the stretch needs (q, k read and written, v read, both cache rows
+    written) for either side."""
+    hq, hkv, d, bs, reps = 32, 8, 128, 16, 16
+    from clearml_serving_amd.models.rope_scaling import rope_inv_freq
+
+    inv_freq = rope_inv_freq(d, 500000.0, None, 8192)[0].cuda()
+    for t in (1, 64, 2048):
+        for kv in ("bf16", "fp8"):
+            qkv = torch.randn(t, (hq + 2 * hkv) * d, device="cuda",
+                              dtype=torch.bfloat16)
+            q, k, v = (x.unflatten(-1, (-1, d)) for x in qkv.split(
+                [hq * d, hkv * d, hkv * d], dim=-1))
+            pos = torch.arange(t, device="cuda", dtype=torch.int32) + 1000
+            slots = torch.arange(t, device="cuda", dtype=torch.int32)
+            nb = (t + bs - 1) // bs
+            kc = torch.zeros(nb, hkv, bs, d, device="cuda",
+                             dtype=torch.uint8 if kv == "fp8"
+                             else torch.bfloat16)
+            vc = torch.zeros_like(kc)
+            sc = ((torch.ones(nb, hkv, bs, device="cuda"),
+                   torch.ones(nb, hkv, bs, device="cuda"))
+                  if kv == "fp8" else (None, None))
+
+            def pair():
+                ops.rope_inplace(q, k, pos, theta=500000.0)
+                ops.kv_cache_write(k, v, kc, vc, slots, *sc)
+
+            def fused():
+                ops.qk_rope_kv(q, k, v, pos, inv_freq, 1.0, None, None, 1e-6,
+                               kc, vc, slots, *sc)
+
+            graphs = {}
+            for name, fn in (("rope+kv_write", pair), ("qk_rope_kv", fused)):
+                fn()
+                torch.cuda.synchronize()
+                graphs[name] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[name]):
+                    for _ in range(reps):
+                        fn()
+            runs = {}
+            for _ in range(3):
+                for name, graph in graphs.items():
+                    runs.setdefault(name, []).append(
+                        timeit(graph.replay, iters=200, warmup=20) / reps)
+            nbytes = t * d * (4 * (hq + hkv) + 2 * hkv
+                              + 2 * hkv * kc.element_size())
+            for name in graphs:
+                lo, dt, hi = sorted(runs[name])
+                results.append(dict(
+                    op="{}_{}".format(name, kv),
+                    shape="T={} [{:.2f}-{:.2f}us]".format(t, lo * 1e6,
+                                                          hi * 1e6),
+                    us=dt * 1e6, gbps=nbytes / dt / 1e9))
+
+
 BENCHES = {"attention": bench_attention, "decode": bench_decode,
            "memops": bench_memops, "gemm": bench_gemm,
            "sampling": bench_sampling, "lora": bench_lora,
            "guided": bench_guided, "moe": bench_moe,
-           "sample_rows": bench_sample_rows}
+           "sample_rows": bench_sample_rows,
+           "qk_rope_kv": bench_qk_rope_kv}
 
 
 def main():

@@ -78,6 +78,9 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor],
                 [hf[p + "self_attn.q_proj.bias"],
                  hf[p + "self_attn.k_proj.bias"],
                  hf[p + "self_attn.v_proj.bias"]], dim=0)
+        if p + "self_attn.q_norm.weight" in hf:  # Qwen3 (qk_norm=True)
+            out[o + "q_norm"] = hf[p + "self_attn.q_norm.weight"]
+            out[o + "k_norm"] = hf[p + "self_attn.k_norm.weight"]
         out[o + "o_proj.weight"] = hf[p + "self_attn.o_proj.weight"]
         out[o + "attn_norm"] = hf[p + "input_layernorm.weight"]
         out[o + "mlp_norm"] = hf[p + "post_attention_layernorm.weight"]
@@ -88,8 +91,48 @@ def convert_hf_llama(hf: Dict[str, torch.Tensor],
     return out
 
 
-# Qwen2 checkpoints use llama key names + QKV biases (handled above)
+# Qwen2 checkpoints use llama key names + QKV biases, Qwen3 (dense) llama
+# key names + q_norm / k_norm weights (both handled above)
 convert_hf_qwen2 = convert_hf_llama
+
+
+def llama_config_from_hf(hf_cfg: dict, **overrides):
+    """A HuggingFace ``config.json`` dict (llama, mistral, qwen2, qwen3) ->
+    LlamaConfig. RoPE parameters are read from ``rope_parameters``
+    (transformers 5) or ``rope_theta`` + ``rope_scaling`` (earlier)."""
+    from .llama import LlamaConfig
+
+    model_type = str(hf_cfg.get("model_type", "llama"))
+    if model_type not in ("llama", "mistral", "qwen2", "qwen3"):
+        raise ValueError("model_type '{}' is not a dense llama-family "
+                         "model".format(model_type))
+    rope = dict(hf_cfg.get("rope_parameters") or hf_cfg.get("rope_scaling")
+                or {})
+    theta = rope.pop("rope_theta", hf_cfg.get("rope_theta", 10000.0))
+    kind = rope.get("rope_type", rope.get("type", "default"))
+    heads = hf_cfg["num_attention_heads"]
+    head_dim = hf_cfg.get("head_dim") or hf_cfg["hidden_size"] // heads
+    # Mistral / Qwen2 configs carry a window that use_sliding_window gates
+    window = hf_cfg.get("sliding_window") or 0
+    if not hf_cfg.get("use_sliding_window", model_type == "mistral"):
+        window = 0
+    fields = dict(
+        vocab_size=hf_cfg["vocab_size"], hidden=hf_cfg["hidden_size"],
+        layers=hf_cfg["num_hidden_layers"], heads=heads,
+        kv_heads=hf_cfg.get("num_key_value_heads") or heads,
+        intermediate=hf_cfg["intermediate_size"], rope_theta=float(theta),
+        rms_eps=hf_cfg.get("rms_norm_eps", 1e-6),
+        max_position=hf_cfg.get("max_position_embeddings", 8192),
+        tie_embeddings=bool(hf_cfg.get("tie_word_embeddings", False)),
+        qkv_bias=bool(hf_cfg.get("attention_bias", model_type == "qwen2")),
+        sliding_window=int(window),
+        rope_scaling=rope if kind != "default" else None,
+        qk_norm=model_type == "qwen3",
+        head_dim_override=(head_dim
+                           if head_dim != hf_cfg["hidden_size"] // heads
+                           else 0))
+    fields.update(overrides)
+    return LlamaConfig(**fields)
 
 
 def _is_hf_mixtral(hf: Dict[str, torch.Tensor]) -> bool:
@@ -181,7 +224,8 @@ def convert_hf_gpt2(hf: Dict[str, torch.Tensor],
 
 def convert_hf_auto(hf: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """Detect a raw HuggingFace state dict by its key layout and convert it
-    to the matching native layout (llama/qwen2, mixtral, gpt2, or bert). Native-
+    to the matching native layout (llama/qwen2/qwen3, mixtral, gpt2, or
+    bert; Qwen3 is the llama layout plus its q_norm / k_norm keys). Native-
     layout dicts pass through unchanged -- callers can always route
     through this."""
     def n_layers(prefix, probe):

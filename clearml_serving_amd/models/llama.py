@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from .. import ops
 from . import register_arch
+from .rope_scaling import rope_inv_freq
 
 
 @dataclass
@@ -48,10 +49,24 @@ class LlamaConfig:
     # sliding-window attention (Mistral): position i sees keys j with
     # i - sliding_window < j <= i; 0 = full context
     sliding_window: int = 0
+    # HuggingFace rope_scaling / rope_parameters dict (linear, llama3, yarn;
+    # models/rope_scaling.py). None = plain RoPE from rope_theta
+    rope_scaling: Optional[dict] = None
+    # Qwen3: per-head RMSNorm on q and k before RoPE
+    qk_norm: bool = False
+    # head size when it is not hidden // heads (Qwen3-0.6B: 1024 / 16 heads
+    # with head_dim 128); 0 = derived
+    head_dim_override: int = 0
 
     @property
     def head_dim(self) -> int:
-        return self.hidden // self.heads
+        return self.head_dim_override or self.hidden // self.heads
+
+    @property
+    def fused_qk_rope(self) -> bool:
+        """Scaled RoPE and the q/k norm run in ops.qk_rope_kv; every other
+        config keeps rope_inplace + kv_cache_write."""
+        return bool(self.rope_scaling) or self.qk_norm
 
 
 class LlamaLayer(nn.Module):
@@ -87,6 +102,26 @@ class LlamaLayer(nn.Module):
             self.gate_up = nn.Linear(h, 2 * inter, bias=False)
             self.down = nn.Linear(inter, h, bias=False)
         self.inter = inter
+        # q/k norm weights cover one head, so they replicate under TP
+        if cfg.qk_norm:
+            self.q_norm = nn.Parameter(torch.ones(hd))
+            self.k_norm = nn.Parameter(torch.ones(hd))
+        else:
+            self.q_norm = self.k_norm = None
+        self._inv_freq_f32, self.attn_factor = None, 1.0
+        if cfg.fused_qk_rope:
+            self._inv_freq_f32, self.attn_factor = rope_inv_freq(
+                hd, cfg.rope_theta, cfg.rope_scaling, cfg.max_position)
+            self.register_buffer("inv_freq", self._inv_freq_f32.clone(),
+                                 persistent=False)
+
+    def _apply(self, fn, recurse=True):
+        # model.to(bf16) casts floating buffers; the frequency table must
+        # stay exact float32, so it is restored from the host copy
+        super()._apply(fn, recurse)
+        if self._inv_freq_f32 is not None:
+            self.inv_freq = self._inv_freq_f32.to(self.inv_freq.device)
+        return self
 
     @staticmethod
     def _proj(mod, x):
@@ -153,8 +188,7 @@ class LlamaLayer(nn.Module):
         q = q.unflatten(-1, (self.heads, self.head_dim))
         k = k.unflatten(-1, (self.kv_heads, self.head_dim))
         v = v.unflatten(-1, (self.kv_heads, self.head_dim))
-        q, k = ops.rope_inplace(q, k, positions, theta=cfg.rope_theta)
-
+        k_cache = v_cache = k_sc = v_sc = slots = None
         if kv_cache is not None:
             # 2-tuple (k, v) bf16 cache, or 4-tuple (k8, v8, k_scale,
             # v_scale) fp8 cache (engine cfg kv_dtype="fp8"): e4m3 bytes +
@@ -162,8 +196,17 @@ class LlamaLayer(nn.Module):
             k_cache, v_cache = kv_cache[0], kv_cache[1]
             k_sc = kv_cache[2] if len(kv_cache) > 2 else None
             v_sc = kv_cache[3] if len(kv_cache) > 2 else None
-            ops.kv_cache_write(k, v, k_cache, v_cache,
-                               attn_ctx["slot_mapping"], k_sc, v_sc)
+            slots = attn_ctx["slot_mapping"]
+        if cfg.fused_qk_rope:
+            # q/k norm + table-driven RoPE + KV write in one launch
+            q, k = ops.qk_rope_kv(q, k, v, positions, self.inv_freq,
+                                  self.attn_factor, self.q_norm, self.k_norm,
+                                  cfg.rms_eps, k_cache, v_cache, slots, k_sc,
+                                  v_sc)
+        else:
+            q, k = ops.rope_inplace(q, k, positions, theta=cfg.rope_theta)
+            if kv_cache is not None:
+                ops.kv_cache_write(k, v, k_cache, v_cache, slots, k_sc, v_sc)
 
         scale = 1.0 / math.sqrt(self.head_dim)
         window = cfg.sliding_window  # model constant, same on every rank
@@ -407,6 +450,42 @@ PRESETS = {
                                 kv_heads=2, intermediate=512,
                                 rope_theta=10000.0, max_position=512,
                                 sliding_window=24),
+    # Llama-3.1 / 3.2: Llama-3 + rope_scaling "llama3". Qwen3 (dense): q/k
+    # norm, no QKV bias, head_dim a field of its own. The full-size numbers
+    # below could not be checked against the hub from here; real checkpoints
+    # take their shape from config.json (models/convert.py
+    # llama_config_from_hf). Numerics pinned vs transformers in
+    # tests/test_qwen3_llama31_cpu.py.
+    "llama-3.1-8b": LlamaConfig(max_position=131072, rope_scaling={
+        "rope_type": "llama3", "factor": 8.0, "low_freq_factor": 1.0,
+        "high_freq_factor": 4.0, "original_max_position_embeddings": 8192}),
+    "llama-3.2-1b": LlamaConfig(
+        hidden=2048, layers=16, heads=32, kv_heads=8, intermediate=8192,
+        tie_embeddings=True, max_position=131072, rope_scaling={
+            "rope_type": "llama3", "factor": 32.0, "low_freq_factor": 1.0,
+            "high_freq_factor": 4.0,
+            "original_max_position_embeddings": 8192}),
+    "qwen3-8b": LlamaConfig(vocab_size=151936, hidden=4096, layers=36,
+                            heads=32, kv_heads=8, intermediate=12288,
+                            rope_theta=1e6, rms_eps=1e-6, max_position=40960,
+                            qk_norm=True, head_dim_override=128),
+    "qwen3-0.6b": LlamaConfig(vocab_size=151936, hidden=1024, layers=28,
+                              heads=16, kv_heads=8, intermediate=3072,
+                              rope_theta=1e6, rms_eps=1e-6,
+                              max_position=40960, tie_embeddings=True,
+                              qk_norm=True, head_dim_override=128),
+    # original max 32 with factor 8: positions >= 32 reach all three bands
+    "llama-3.1-tiny": LlamaConfig(
+        vocab_size=512, hidden=256, layers=2, heads=4, kv_heads=2,
+        intermediate=512, rope_theta=10000.0, max_position=512,
+        rope_scaling={"rope_type": "llama3", "factor": 8.0,
+                      "low_freq_factor": 1.0, "high_freq_factor": 4.0,
+                      "original_max_position_embeddings": 32}),
+    # head_dim 128 with hidden 256 / 4 heads: the override is exercised
+    "qwen3-tiny": LlamaConfig(vocab_size=512, hidden=256, layers=2, heads=4,
+                              kv_heads=2, intermediate=512, rope_theta=1e6,
+                              rms_eps=1e-6, max_position=512, qk_norm=True,
+                              head_dim_override=128),
 }
 
 

@@ -573,6 +573,59 @@ def rope_inplace(
     return q, k
 
 
+def qk_rope_kv(
+    q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+    positions: torch.Tensor, inv_freq: torch.Tensor,
+    attn_factor: float = 1.0,
+    q_norm_w: Optional[torch.Tensor] = None,
+    k_norm_w: Optional[torch.Tensor] = None, eps: float = 1e-6,
+    k_cache: Optional[torch.Tensor] = None,
+    v_cache: Optional[torch.Tensor] = None,
+    slot_mapping: Optional[torch.Tensor] = None,
+    k_scale: Optional[torch.Tensor] = None,
+    v_scale: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Fused per-head RMSNorm (optional) + scaled RoPE + paged KV write, the
+    stretch between the QKV projection and attention in one launch.
+
+    q [T, Hq, D], k/v [T, Hkv, D] (token-strided views of the merged QKV
+    output), positions int32 [T], inv_freq float32 [D/2] (models/
+    rope_scaling.py). Per head row in fp32: x * rsqrt(mean(x^2) + eps) * w
+    when norm weights ([D]) are given, then NeoX pairs (i, i + D/2) rotate by
+    float(pos) * inv_freq[i] with cos/sin scaled by ``attn_factor``; one
+    rounding to the model dtype, stored in place. With caches, the rounded k
+    row and the v row also go to their slot (kv_cache_write semantics, fp8
+    included; slot -1 skips the cache and still rotates)."""
+    caches = (k_cache, v_cache, slot_mapping)
+    if any(c is None for c in caches) != all(c is None for c in caches):
+        raise ValueError("k_cache, v_cache and slot_mapping are all given "
+                         "or all absent")
+    if (q_norm_w is None) != (k_norm_w is None):
+        raise ValueError("q_norm_w and k_norm_w come together")
+    if q.is_cuda:
+        ext = _require_ext("qk_rope_kv")
+        if ext is not None:
+            ext.qk_rope_kv(q, k, v, positions, inv_freq, float(attn_factor),
+                           q_norm_w, k_norm_w, float(eps), k_cache, v_cache,
+                           slot_mapping, k_scale, v_scale)
+            return q, k
+    half = q.shape[-1] // 2
+    angles = positions.float()[:, None] * inv_freq.float()[None, :]
+    cos = (angles.cos() * float(attn_factor))[:, None, :]
+    sin = (angles.sin() * float(attn_factor))[:, None, :]
+    for t, w in ((q, q_norm_w), (k, k_norm_w)):
+        tf = t.float().clone()  # see rope_inplace: no aliasing of lo/hi
+        if w is not None:
+            tf = tf * torch.rsqrt(tf.pow(2).mean(-1, keepdim=True) + eps) \
+                * w.float()
+        lo, hi = tf[..., :half], tf[..., half:]
+        t[..., :half] = (lo * cos - hi * sin).to(t.dtype)
+        t[..., half:] = (hi * cos + lo * sin).to(t.dtype)
+    if k_cache is not None:
+        kv_cache_write(k, v, k_cache, v_cache, slot_mapping, k_scale, v_scale)
+    return q, k
+
+
 # --------------------------------------------------------------------- #
 # Sampling
 # --------------------------------------------------------------------- #

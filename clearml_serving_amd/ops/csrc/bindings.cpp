@@ -81,6 +81,15 @@ torch::Tensor moe_experts_fp8(torch::Tensor x8, torch::Tensor x_scale,
                               torch::Tensor w2_8, torch::Tensor w2_scale,
                               torch::Tensor ids, torch::Tensor weights,
                               int64_t block_m);
+void qk_rope_kv(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                torch::Tensor positions, torch::Tensor inv_freq,
+                double attn_factor, c10::optional<torch::Tensor> q_norm_w,
+                c10::optional<torch::Tensor> k_norm_w, double eps,
+                c10::optional<torch::Tensor> k_cache,
+                c10::optional<torch::Tensor> v_cache,
+                c10::optional<torch::Tensor> slot_mapping,
+                c10::optional<torch::Tensor> k_scale,
+                c10::optional<torch::Tensor> v_scale);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "clearml-serving-amd gfx950 kernel library";
@@ -151,4 +160,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x_scale"), py::arg("w13_8"), py::arg("w13_scale"),
         py::arg("w2_8"), py::arg("w2_scale"), py::arg("ids"),
         py::arg("weights"), py::arg("block_m") = 16);
+  m.def("qk_rope_kv", &qk_rope_kv, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("positions"), py::arg("inv_freq"),
+        py::arg("attn_factor") = 1.0, py::arg("q_norm_w") = py::none(),
+        py::arg("k_norm_w") = py::none(), py::arg("eps") = 1e-6,
+        py::arg("k_cache") = py::none(), py::arg("v_cache") = py::none(),
+        py::arg("slot_mapping") = py::none(),
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
 }
