@@ -421,12 +421,79 @@ def bench_qk_rope_kv(results):
                     us=dt * 1e6, gbps=nbytes / dt / 1e9))
 
 
+def bench_mxfp4(results):
+    """ops.skinny_gemm_mxfp4 (csrc/mxfp4_path.hip, 4 and 8 k-split waves) at
+    the Llama-3-8B projection shapes against ops.skinny_gemm_fp8 on the same
+    weights in e4m3 and against Mxfp4Linear's dequant + bf16 matmul route.
+    Decode streams every layer's weights once per step, so each side runs
+    over enough clones of its weight to exceed the 256 MiB last-level cache
+    (at least 8), one call per clone captured into a graph; the graphs are
+    replayed alternately and the median of three rounds is kept. us is per
+    call; GB/s counts the weight bytes of the side (elements + scales)."""
+    from clearml_serving_amd.models.quant import F8, F8_MAX
+
+    shapes = (("qkv", 6144, 4096), ("o_proj", 4096, 4096),
+              ("gate_up", 28672, 4096), ("down", 4096, 14336))
+    for name, n, k in shapes:
+        w = torch.randn(n, k, device="cuda") / 32
+        w4, e8, rs = ops.quantize_mxfp4(w)
+        w4t, e8t = ops.tile_mxfp4_weight(w4, e8)
+        ws8 = w.abs().amax(dim=1) / F8_MAX
+        w8 = ops.swizzle_fp8_weight((w / ws8[:, None]).to(F8).view(torch.uint8))
+        del w, w4, e8
+        mx_bytes, f8_bytes = w4t.numel() + e8t.numel(), w8.numel()
+        mx = [(w4t.clone(), e8t.clone())
+              for _ in range(max(8, -(-(300 << 20) // mx_bytes)))]
+        f8 = [w8.clone() for _ in range(max(8, -(-(300 << 20) // f8_bytes)))]
+        for m in (1, 8, 16, 32, 64):
+            x8, xs = ops.quant_fp8(torch.randn(m, k, device="cuda",
+                                               dtype=torch.bfloat16))
+
+            def dequant_route(wt, et):
+                wd = ops.dequant_mxfp4_bf16(wt, et, rs, n, k)
+                return (x8.view(F8).to(torch.bfloat16) @ wd.t()).float() \
+                    * xs[:, None]
+
+            sides = {
+                "mxfp4_w4": lambda: [ops.skinny_gemm_mxfp4(
+                    x8, xs, wt, et, rs, waves=4) for wt, et in mx],
+                "mxfp4_w8": lambda: [ops.skinny_gemm_mxfp4(
+                    x8, xs, wt, et, rs, waves=8) for wt, et in mx],
+                "fp8_skinny": lambda: [ops.skinny_gemm_fp8(
+                    x8, xs, wq, ws8, swizzled=True) for wq in f8],
+                "mxfp4_dequant+mm": lambda: [dequant_route(wt, et)
+                                             for wt, et in mx[:8]],
+            }
+            calls = {"fp8_skinny": len(f8), "mxfp4_dequant+mm": 8}
+            graphs = {}
+            for side, fn in sides.items():
+                fn()
+                torch.cuda.synchronize()
+                graphs[side] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[side]):
+                    fn()
+            runs = {}
+            for _ in range(3):
+                for side, graph in graphs.items():
+                    runs.setdefault(side, []).append(
+                        timeit(graph.replay, iters=100, warmup=5)
+                        / calls.get(side, len(mx)))
+            for side in graphs:
+                lo, dt, hi = sorted(runs[side])
+                results.append(dict(
+                    op=side, shape="{} M={} [{:.1f}-{:.1f}us]".format(
+                        name, m, lo * 1e6, hi * 1e6), us=dt * 1e6,
+                    gbps=(f8_bytes if side == "fp8_skinny" else mx_bytes)
+                    / dt / 1e9))
+            del graphs
+
+
 BENCHES = {"attention": bench_attention, "decode": bench_decode,
            "memops": bench_memops, "gemm": bench_gemm,
            "sampling": bench_sampling, "lora": bench_lora,
            "guided": bench_guided, "moe": bench_moe,
            "sample_rows": bench_sample_rows,
-           "qk_rope_kv": bench_qk_rope_kv}
+           "qk_rope_kv": bench_qk_rope_kv, "mxfp4": bench_mxfp4}
 
 
 def main():

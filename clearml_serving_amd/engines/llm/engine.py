@@ -295,7 +295,8 @@ class LlmEngineConfig:
                                # interleaves between chunks of long prompts)
     gpu_memory_fraction: float = 0.85
     num_kv_blocks: Optional[int] = None  # explicit override (CPU tests)
-    quantization: Optional[str] = None   # "fp8": fp8 weights via hipBLASLt
+    quantization: Optional[str] = None   # "fp8": fp8 weights via hipBLASLt;
+    # "mxfp4": OCP MX e2m1 weights on the block-scaled MFMA (dense models)
     kv_dtype: str = "bfloat16"  # "fp8": e4m3 KV cache + per-token-per-head
                                 # scales -- 2x cached tokens per HBM byte,
                                 # half the KV reads on long-context decode
@@ -687,6 +688,18 @@ class LlmEngine:
                     "fp8 quantization covers the llama-family projections "
                     "only (arch '{}' has none)".format(cfg.arch))
             print("[llm] fp8-quantized {} projection layers".format(n))
+        elif cfg.quantization == "mxfp4":
+            if self.device.type != "cuda":
+                raise ValueError("mxfp4 quantization needs a GPU (gfx950 "
+                                 "block-scaled MFMA)")
+            from ...models.quant import quantize_llama_mxfp4
+
+            n = quantize_llama_mxfp4(self.model)
+            if n == 0:
+                raise ValueError(
+                    "mxfp4 quantization covers the llama-family projections "
+                    "only (arch '{}' has none)".format(cfg.arch))
+            print("[llm] mxfp4-quantized {} projection layers".format(n))
         if lora_adapters:
             from ...models.lora import LoraBank
 
@@ -796,6 +809,10 @@ class LlmEngine:
             raise ValueError(
                 "sliding_window={} is not supported for mixture-of-experts "
                 "models (num_experts={})".format(window, n_exp))
+        if cfg.quantization == "mxfp4":
+            raise ValueError(
+                "quantization='mxfp4' covers dense models only "
+                "(num_experts={}): use 'fp8' for expert weights".format(n_exp))
         if cfg.quantization == "fp8" and self.device.type != "cuda":
             raise ValueError(
                 "quantization='fp8' for mixture-of-experts models "
@@ -893,11 +910,11 @@ class LlmEngine:
         if gpt2:
             raise ValueError("lora_modules serve the llama family only "
                              "(arch=gpt2 has no adapter hook)")
-        if cfg.quantization == "fp8":
+        if cfg.quantization in ("fp8", "mxfp4"):
             raise ValueError(
-                "lora_modules are not supported with quantization='fp8': "
+                "lora_modules are not supported with quantization='{}': "
                 "the fp8 path never materialises the bf16 activation the "
-                "adapter reads")
+                "adapter reads".format(cfg.quantization))
         if self.tp_size > 1:
             raise ValueError("lora_modules are not supported under tensor "
                              "parallelism (tp_size={})".format(self.tp_size))

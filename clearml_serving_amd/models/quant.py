@@ -14,6 +14,11 @@ Scheme: per-output-row weight scales (absmax/448), dynamic per-row (token)
 activation scales. Enable per endpoint via model card / aux
 ``{"quantization": "fp8"}``. The reference delegates all quantization to
 vLLM (preprocess_service.py:619-1095).
+
+``{"quantization": "mxfp4"}`` (dense llama-family models) halves the weight
+bytes again: OCP MX e2m1 weights with an e8m0 scale per 32 k-values, taken
+directly by the gfx950 block-scaled MFMA against the same fused fp8
+activations (Mxfp4Linear, ops/csrc/mxfp4_path.hip).
 """
 
 import torch
@@ -136,6 +141,90 @@ class Fp8Linear(nn.Module):
         x8, xs = ops.quant_fp8(x2)
         out = self.forward_q(x8, xs, out_dtype=x.dtype)
         return out.reshape(*orig_shape[:-1], self.out_features)
+
+
+class Mxfp4Linear(nn.Module):
+    """nn.Linear replacement: MXFP4 weights (OCP MX e2m1 + e8m0 scale per 32
+    k-values, ops.quantize_mxfp4; row scale all ones) against the same e4m3
+    activations Fp8Linear takes, with the same forward / forward_q surface
+    and the same bias handling. Only the kernel-tiled copy of the weight
+    (ops.tile_mxfp4_weight) lives in HBM: 4.25 bits per weight.
+
+    Routing: decode-shaped rows on eligible shapes (K % 128 == 0,
+    N % 16 == 0) run ops.skinny_gemm_mxfp4, the block-scaled MFMA kernel.
+    Everything else -- larger M, other shapes (e.g. TP shards), CPU tensors
+    -- dequantises the whole weight to a transient bf16 [N, K] buffer
+    (ops.dequant_mxfp4_bf16: 2 bytes per weight written and read back, and
+    N*K*2 bytes of peak memory per call) and runs a bf16 matmul on the
+    dequantised activations. A tiled mxfp4 prefill kernel is out of scope."""
+
+    # largest M at which skinny_gemm_mxfp4 beats the dequant + matmul route
+    # on every Llama-3-8B projection shape (profiles/mxfp4_kernels.txt: at
+    # M=64 12-60 us against 46-195 us); 64 is also the kernel's own limit
+    SKINNY_MAX_M = 64
+
+    def __init__(self, linear: nn.Linear):
+        super().__init__()
+        w4, e8, row_scale = ops.quantize_mxfp4(linear.weight.data)
+        w4t, e8t = ops.tile_mxfp4_weight(w4, e8)
+        self.register_buffer("weight_mx", w4t)
+        self.register_buffer("scale_mx", e8t)
+        self.register_buffer("weight_scale", row_scale)  # [N] fp32
+        self.out_features = linear.out_features
+        self.in_features = linear.in_features
+        self.out_dtype = linear.weight.dtype
+        if linear.bias is not None:
+            self.register_buffer("bias", linear.bias.data.clone())
+        else:
+            self.bias = None
+
+    def _route(self, m: int) -> str:
+        n, k = self.out_features, self.in_features
+        if m <= self.SKINNY_MAX_M and k % 128 == 0 and n % 16 == 0:
+            return "skinny"
+        return "dequant"
+
+    def forward_q(self, x8: torch.Tensor, x_scale: torch.Tensor,
+                  out_dtype=None) -> torch.Tensor:
+        out_dtype = out_dtype or self.out_dtype
+        if x8.is_cuda and self._route(x8.shape[0]) == "skinny":
+            out = ops.skinny_gemm_mxfp4(x8, x_scale, self.weight_mx,
+                                        self.scale_mx, self.weight_scale)
+        else:
+            w = ops.dequant_mxfp4_bf16(self.weight_mx, self.scale_mx,
+                                       self.weight_scale, self.out_features,
+                                       self.in_features)
+            # e4m3 is exact in bf16; the row scale goes on in fp32 after
+            out = (x8.view(F8).to(torch.bfloat16) @ w.t()).float() \
+                * x_scale[:, None]
+        out = out if out.dtype == out_dtype else out.to(out_dtype)
+        if self.bias is not None:
+            out = out + self.bias.to(out_dtype)
+        return out
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        orig_shape = x.shape
+        x8, xs = ops.quant_fp8(x.reshape(-1, orig_shape[-1]))
+        out = self.forward_q(x8, xs, out_dtype=x.dtype)
+        return out.reshape(*orig_shape[:-1], self.out_features)
+
+
+def quantize_llama_mxfp4(model: nn.Module) -> int:
+    """Swap the projection Linears (qkv, o_proj, gate_up, down) of a dense
+    LlamaForCausalLM to Mxfp4Linear; lm_head stays bf16. Mixture-of-experts
+    layers are refused. Returns the number of projections converted."""
+    layers = list(getattr(model, "layers", []))
+    if any(hasattr(layer, "w13") for layer in layers):
+        raise ValueError("quantization='mxfp4' covers dense models only: "
+                         "this model has expert layers (use 'fp8')")
+    n = 0
+    for layer in layers:
+        for name in ("qkv", "o_proj", "gate_up", "down"):
+            lin = getattr(layer, name, None)
+            if isinstance(lin, nn.Linear):
+                setattr(layer, name, Mxfp4Linear(lin))
+                n += 1
+    return n
 
 
 def quantize_experts_fp8(w: torch.Tensor):

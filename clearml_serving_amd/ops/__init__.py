@@ -257,6 +257,121 @@ def skinny_gemm_fp8_v2(a8: torch.Tensor, a_scale: torch.Tensor,
     return (a @ w.t()).to(torch.bfloat16)
 
 
+# --------------------------------------------------------------------- #
+# MXFP4 weights (OCP MX: e2m1 elements, one e8m0 scale per 32 k-values) on
+# the gfx950 block-scaled MFMA (kernels: csrc/mxfp4_path.hip). Activations
+# are the e4m3 rows + row scales of the fp8 producers above.
+# --------------------------------------------------------------------- #
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    """[N, K] (K % 32 == 0) -> (w4 uint8 [N, K/2], e8 uint8 [N, K/32],
+    row_scale fp32 [N]) by the OCP MX rule: per block of 32 along K the
+    shared exponent is floor(log2(amax)) - 2 clamped to the e8m0 range (an
+    all-zero block gets 2^0), elements are rounded to nearest-even onto the
+    e2m1 grid and saturate at +-6; even k sits in the low nibble.
+
+    row_scale is ALL ONES: pure MX. A per-row fp32 pre-scale cannot move a
+    block's power-of-two exponent by less than one step, so it only helps the
+    row's largest block; it stays an input of the kernels and of
+    dequant_mxfp4 so that a checkpoint carrying one can be served."""
+    n, k = w.shape
+    if k % 32:
+        raise ValueError("quantize_mxfp4: K ({}) must be a multiple of the "
+                         "MX block size 32".format(k))
+    blocks = w.detach().float().reshape(n, k // 32, 32)
+    amax = blocks.abs().amax(dim=2)
+    # frexp: amax = m * 2^e with m in [0.5, 1), so floor(log2(amax)) = e - 1
+    exp = (torch.frexp(amax)[1] - 3).clamp(-127, 127)
+    exp = torch.where(amax > 0, exp, torch.zeros_like(exp))
+    a = torch.ldexp(blocks, -exp[:, :, None]).abs()
+    # e2m1 code = number of round-up thresholds passed; the midpoints whose
+    # upper neighbour has an even mantissa (.75, 1.75, 3.5) round up on a tie
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25)
+            + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+    nib = (code | ((blocks < 0).to(torch.uint8) << 3)).reshape(n, k)
+    w4 = (nib[:, 0::2] | (nib[:, 1::2] << 4)).contiguous()
+    e8 = (exp + 127).to(torch.uint8)
+    return w4, e8, torch.ones(n, dtype=torch.float32, device=w.device)
+
+
+def dequant_mxfp4(w4: torch.Tensor, e8: torch.Tensor,
+                  row_scale: torch.Tensor) -> torch.Tensor:
+    """Plain inverse of quantize_mxfp4 -> fp32 [N, K]: the numerics oracle
+    and the CPU path of the mxfp4 ops."""
+    n = w4.shape[0]
+    nib = torch.stack((w4 & 0xF, w4 >> 4), dim=2).reshape(n, -1).long()
+    grid = torch.tensor(E2M1_GRID + tuple(-v for v in E2M1_GRID),
+                        dtype=torch.float32, device=w4.device)
+    vals = grid[nib].reshape(n, -1, 32)
+    w = torch.ldexp(vals, e8.to(torch.int32)[:, :, None] - 127)
+    return w.reshape(n, -1) * row_scale.float()[:, None]
+
+
+def tile_mxfp4_weight(w4: torch.Tensor, e8: torch.Tensor):
+    """Load-time re-layout for csrc/mxfp4_path.hip (layout comment there):
+    w4 [N, K/2] -> [ceil(N/16), ceil(K/128), 64, 16], lane (r, g) = 16g + r
+    holding row 16nb + r, k = 128ks + 32g .. +31, so a wave's 16-byte load is
+    one contiguous 1 KiB line; e8 [N, K/32] -> [ceil(N/16), ceil(K/512), 64,
+    4], byte j of lane (r, g) scaling k-step 4q + j, block g. N and K are
+    padded (zero elements, scale 127 = 2^0)."""
+    n, kb = e8.shape
+    pn, steps = (-n) % 16, (kb + 3) // 4
+    quads = (steps + 3) // 4
+    F = torch.nn.functional
+    w4p = F.pad(w4, (0, steps * 64 - w4.shape[1], 0, pn))
+    e8p = F.pad(e8, (0, quads * 16 - kb, 0, pn), value=127)
+    w4t = w4p.reshape(-1, 16, steps, 4, 16).permute(0, 2, 3, 1, 4)
+    e8t = e8p.reshape(-1, 16, quads, 4, 4).permute(0, 2, 4, 1, 3)
+    return (w4t.reshape(-1, steps, 64, 16).contiguous(),
+            e8t.reshape(-1, quads, 64, 4).contiguous())
+
+
+def untile_mxfp4_weight(w4t: torch.Tensor, e8t: torch.Tensor, n: int, k: int):
+    """Inverse of tile_mxfp4_weight, cropped to the true [N, K]."""
+    nb, steps = w4t.shape[:2]
+    w4 = w4t.reshape(nb, steps, 4, 16, 16).permute(0, 3, 1, 2, 4)
+    e8 = e8t.reshape(nb, -1, 4, 16, 4).permute(0, 3, 1, 4, 2)
+    return (w4.reshape(nb * 16, -1)[:n, :k // 2].contiguous(),
+            e8.reshape(nb * 16, -1)[:n, :k // 32].contiguous())
+
+
+def skinny_gemm_mxfp4(a8: torch.Tensor, a_scale: torch.Tensor,
+                      w4t: torch.Tensor, e8t: torch.Tensor,
+                      w_scale: torch.Tensor, waves: int = 0) -> torch.Tensor:
+    """C[M,N] = (A8*s_a) @ (dequant(W4,E8)*s_w)^T -> bf16 for M <= 64,
+    K % 128 == 0, N % 16 == 0 (N = len(w_scale), K = a8.shape[1]); w4t / e8t
+    in tile_mxfp4_weight layout. One workgroup per 16 columns on
+    mfma_scale_f32_16x16x128_f8f6f4 (e4m3 x e2m1, e8m0 scales applied by the
+    instruction), ``waves`` (4 or 8) split K and reduce through LDS in a
+    fixed order: bit-reproducible, capture-safe. waves=0 takes the measured
+    choice (profiles/mxfp4_kernels.txt): 4 where N/16 workgroups oversubscribe
+    the chip several times (gate_up, 14 vs 17 us at M=1), else 8."""
+    if a8.is_cuda:
+        ext = _require_ext("skinny_gemm_mxfp4")
+        if ext is not None:
+            waves = waves or (4 if w_scale.numel() >= 16384 else 8)
+            return ext.skinny_gemm_mxfp4(a8.view(torch.uint8), a_scale, w4t,
+                                         e8t, w_scale, waves)
+    w = dequant_mxfp4(*untile_mxfp4_weight(w4t, e8t, w_scale.numel(),
+                                           a8.shape[1]), w_scale)
+    a = a8.view(torch.float8_e4m3fn).float() * a_scale[:, None]
+    return (a @ w.t()).to(torch.bfloat16)
+
+
+def dequant_mxfp4_bf16(w4t: torch.Tensor, e8t: torch.Tensor,
+                       w_scale: torch.Tensor, n: int, k: int) -> torch.Tensor:
+    """Tiled mxfp4 weight (* w_scale) -> bf16 [N, K] (any N, K % 32 == 0):
+    the transient operand of Mxfp4Linear's large-M route."""
+    if w4t.is_cuda:
+        ext = _require_ext("dequant_mxfp4_bf16")
+        if ext is not None:
+            return ext.dequant_mxfp4_bf16(w4t, e8t, w_scale, n, k)
+    return dequant_mxfp4(*untile_mxfp4_weight(w4t, e8t, n, k),
+                         w_scale).to(torch.bfloat16)
+
+
 def conv3x3_supported(x: torch.Tensor, w: torch.Tensor) -> bool:
     """True when the in-tree conv kernel serves this shape (3x3 s1 p1,
     ResNet-50 bottleneck widths, bf16 GPU)."""
