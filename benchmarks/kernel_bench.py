@@ -215,7 +215,11 @@ def bench_moe(results):
     as a captured-graph replay; the eager loop reads per-expert row sets
     back to the host (nonzero), so it cannot be captured at all. The same
     weights quantised to e4m3 give the fp8 rows: ops.moe_experts_fp8 fused at
-    both row blocks and its per-expert scaled_mm loop."""
+    both row blocks and its per-expert scaled_mm loop; quantised to MXFP4
+    (csrc/moe_mxfp4.hip, 0.53125 bytes per weight: e2m1 + an e8m0 scale per
+    32) they give the mxfp4 rows: ops.moe_experts_mxfp4 fused at both row
+    blocks and its per-expert dequant + bf16 matmul loop. Every fused row is
+    also timed as a graph replay at T <= 64."""
     h, inter, e, k = 4096, 14336, 8, 2
     g = torch.Generator().manual_seed(0)
     w13 = (torch.randn(e, 2 * inter, h, generator=g) * h ** -0.5
@@ -227,6 +231,9 @@ def bench_moe(results):
     from clearml_serving_amd.models.quant import quantize_experts_fp8
 
     f8 = quantize_experts_fp8(w13) + quantize_experts_fp8(w2)
+    from clearml_serving_amd.models.quant import quantize_experts_mxfp4
+
+    mx = quantize_experts_mxfp4(w13) + quantize_experts_mxfp4(w2)
     for t in (1, 8, 32, 64, 128, 256, 512, 2048):
         x = torch.randn(t, h, generator=g).to(torch.bfloat16).cuda()
         ids, wts = ops.moe_route(torch.randn(t, e, generator=g).cuda(), k)
@@ -247,10 +254,15 @@ def bench_moe(results):
                 x8, xs, *f8, ids, wts, block_m=64)),
             ("moe_fp8_loop", lambda: ops._moe_experts_fp8_loop(
                 x8, xs, *f8, ids, wts)),
+            ("moe_mxfp4_fused_bm16", lambda: ops.moe_experts_mxfp4(
+                x8, xs, *mx, ids, wts, block_m=16)),
+            ("moe_mxfp4_fused_bm64", lambda: ops.moe_experts_mxfp4(
+                x8, xs, *mx, ids, wts, block_m=64)),
+            ("moe_mxfp4_loop", lambda: ops._moe_experts_mxfp4_loop(
+                x8, xs, *mx, ids, wts)),
         ]
         if t <= 64:
-            for bm in (16, 64):
-                fn = cases[0 if bm == 16 else 1][1]
+            for op, fn in [c for c in cases if "fused" in c[0]]:
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
@@ -259,8 +271,7 @@ def bench_moe(results):
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
                     fn()
-                cases.append(("moe_fused_bm{}_graph".format(bm),
-                              graph.replay))
+                cases.append((op + "_graph", graph.replay))
         iters = 50 if t <= 64 else 10
         best = {}
         for _ in range(3):  # alternate the variants, keep each one's median
@@ -269,7 +280,9 @@ def bench_moe(results):
                     timeit(fn, iters=iters, warmup=5))
         for op, _fn in cases:
             dt = sorted(best[op])[1]
-            nbytes = bytes_moved / 2 if "fp8" in op else bytes_moved
+            nbytes = (bytes_moved / 2 if "fp8" in op
+                      else bytes_moved / 2 * 0.53125 if "mxfp4" in op
+                      else bytes_moved)
             results.append(dict(op=op, shape=shape, us=dt * 1e6,
                                 gbps=nbytes / dt / 1e9))
 

@@ -809,10 +809,20 @@ class LlmEngine:
             raise ValueError(
                 "sliding_window={} is not supported for mixture-of-experts "
                 "models (num_experts={})".format(window, n_exp))
-        if cfg.quantization == "mxfp4":
+        if cfg.quantization == "mxfp4" and base is not None:
+            # the block-scaled MFMA steps K in 128 (H for gate/up, I for down)
+            dims = {k: int(cfg.overrides.get(k, getattr(base, k)))
+                    for k in ("hidden", "intermediate")}
+            if any(v % 128 for v in dims.values()):
+                raise ValueError(
+                    "quantization='mxfp4' for mixture-of-experts models "
+                    "needs hidden and intermediate to be multiples of 128, "
+                    "got {}".format(dims))
+        if cfg.quantization == "mxfp4" and self.device.type != "cuda":
             raise ValueError(
-                "quantization='mxfp4' covers dense models only "
-                "(num_experts={}): use 'fp8' for expert weights".format(n_exp))
+                "quantization='mxfp4' for mixture-of-experts models "
+                "(num_experts={}) needs a GPU: the mxfp4 expert path is the "
+                "HIP kernels of ops/csrc/moe_mxfp4.hip".format(n_exp))
         if cfg.quantization == "fp8" and self.device.type != "cuda":
             raise ValueError(
                 "quantization='fp8' for mixture-of-experts models "

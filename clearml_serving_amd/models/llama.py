@@ -249,6 +249,20 @@ class LlamaLayer(nn.Module):
         """norm -> gate_up -> silu*up -> down, WITHOUT the row-parallel
         all-reduce (see attn_half). ``lora``: attn_ctx["lora"] or None."""
         cfg = self.cfg
+        if cfg.num_experts > 0 and getattr(self, "w13_e8", None) is not None:
+            # MXFP4 experts (models/quant.py): the fp8 data flow below with
+            # the tiled e2m1 stacks; w13 / w2 are uint8 here too, so the
+            # e8m0 scale buffer is what tells the two apart
+            x8, xs = ops.rmsnorm_fp8(attn_out, self.mlp_norm, cfg.rms_eps,
+                                     residual=residual)
+            dt = attn_out.dtype
+            x = x8.view(torch.float8_e4m3fn).to(dt) * xs.to(dt)[:, None]
+            ids, weights = ops.moe_route(self.router(x), cfg.experts_per_tok,
+                                         cfg.norm_topk_prob)
+            out = ops.moe_experts_mxfp4(
+                x8, xs, self.w13, self.w13_e8, self.w13_scale, self.w2,
+                self.w2_e8, self.w2_scale, ids, weights)
+            return out if out.dtype == dt else out.to(dt)
         if cfg.num_experts > 0 and self.w13.dtype == torch.uint8:
             # fp8 experts (models/quant.py): the norm emits the e4m3 row and
             # its scale in one pass; the router runs on that row dequantised

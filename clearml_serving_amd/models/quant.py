@@ -15,10 +15,13 @@ activation scales. Enable per endpoint via model card / aux
 ``{"quantization": "fp8"}``. The reference delegates all quantization to
 vLLM (preprocess_service.py:619-1095).
 
-``{"quantization": "mxfp4"}`` (dense llama-family models) halves the weight
-bytes again: OCP MX e2m1 weights with an e8m0 scale per 32 k-values, taken
+``{"quantization": "mxfp4"}`` (llama-family models) halves the weight bytes
+again: OCP MX e2m1 weights with an e8m0 scale per 32 k-values, taken
 directly by the gfx950 block-scaled MFMA against the same fused fp8
-activations (Mxfp4Linear, ops/csrc/mxfp4_path.hip).
+activations (Mxfp4Linear, ops/csrc/mxfp4_path.hip). Expert stacks of a
+mixture-of-experts model are quantised the same way, one expert at a time,
+and kept only in the kernel-tiled layout (quantize_experts_mxfp4,
+ops.moe_experts_mxfp4, ops/csrc/moe_mxfp4.hip).
 """
 
 import torch
@@ -209,16 +212,48 @@ class Mxfp4Linear(nn.Module):
         return out.reshape(*orig_shape[:-1], self.out_features)
 
 
+def quantize_experts_mxfp4(w: torch.Tensor):
+    """Expert stack [E, N, K] (N % 16 == 0, K % 128 == 0) -> (e2m1 bytes
+    uint8 [E, N/16, K/128, 64, 16], e8m0 scales uint8 [E, N/16, ceil(K/512),
+    64, 4], fp32 row scales [E, N], all ones): every expert quantised by
+    ops.quantize_mxfp4 and kept in the ops.tile_mxfp4_weight layout, the
+    operands of ops.moe_experts_mxfp4. One expert at a time, so the fp32
+    temporaries stay at one expert's size."""
+    e, n, k = w.shape
+    if n % 16 or k % 128:
+        raise ValueError("quantize_experts_mxfp4: need N % 16 == 0 and "
+                         "K % 128 == 0, got N={} K={}".format(n, k))
+    steps = k // 128
+    w4t = torch.empty(e, n // 16, steps, 64, 16, dtype=torch.uint8,
+                      device=w.device)
+    e8t = torch.empty(e, n // 16, (steps + 3) // 4, 64, 4, dtype=torch.uint8,
+                      device=w.device)
+    scale = torch.empty(e, n, dtype=torch.float32, device=w.device)
+    for i in range(e):
+        w4, e8, scale[i] = ops.quantize_mxfp4(w[i])
+        w4t[i], e8t[i] = ops.tile_mxfp4_weight(w4, e8)
+    return w4t, e8t, scale
+
+
 def quantize_llama_mxfp4(model: nn.Module) -> int:
-    """Swap the projection Linears (qkv, o_proj, gate_up, down) of a dense
-    LlamaForCausalLM to Mxfp4Linear; lm_head stays bf16. Mixture-of-experts
-    layers are refused. Returns the number of projections converted."""
-    layers = list(getattr(model, "layers", []))
-    if any(hasattr(layer, "w13") for layer in layers):
-        raise ValueError("quantization='mxfp4' covers dense models only: "
-                         "this model has expert layers (use 'fp8')")
+    """Swap the projection Linears (qkv, o_proj, gate_up, down) of a
+    LlamaForCausalLM to Mxfp4Linear; lm_head stays bf16. A layer with experts
+    also gets its ``w13`` / ``w2`` stacks replaced by tiled e2m1 buffers of
+    the same names plus ``w13_e8`` / ``w2_e8`` (tiled e8m0 scales) and
+    ``w13_scale`` / ``w2_scale`` (quantize_experts_mxfp4); the bf16
+    parameters are dropped and the router stays in the model dtype. Returns
+    the number of projections and expert stacks converted."""
     n = 0
-    for layer in layers:
+    for layer in getattr(model, "layers", []):
+        for name in ("w13", "w2"):
+            w = getattr(layer, name, None)
+            if isinstance(w, nn.Parameter):
+                w4t, e8t, scale = quantize_experts_mxfp4(w.data)
+                delattr(layer, name)
+                layer.register_buffer(name, w4t)
+                layer.register_buffer(name + "_e8", e8t)
+                layer.register_buffer(name + "_scale", scale)
+                n += 1
         for name in ("qkv", "o_proj", "gate_up", "down"):
             lin = getattr(layer, name, None)
             if isinstance(lin, nn.Linear):

@@ -1459,6 +1459,156 @@ def moe_experts_fp8(x8: torch.Tensor, x_scale: torch.Tensor,
                                 w2_scale, ids, weights)
 
 
+# --------------------------------------------------------------------- #
+# Mixture of experts with MXFP4 expert weights (kernels:
+# csrc/moe_mxfp4.hip)
+# --------------------------------------------------------------------- #
+# Path threshold of moe_experts_mxfp4. It started at MOE_FP8_FUSED_MAX (256);
+# the mxfp4 table in profiles/moe_bench.txt has the fused path ahead of the
+# loop (which pays one expert's dequantisation to bf16 per expert and call)
+# at every measured T: 642 vs 3207 us at T=256, 4070 vs 4857 us at T=2048,
+# the largest T measured, so the threshold stands there.
+MOE_MXFP4_FUSED_MAX = int(os.environ.get("CMLS_MOE_MXFP4_FUSED_MAX", "2048"))
+# Row block of the fused mxfp4 path; it started at MOE_BLOCK16_MAX (64). Same
+# table: 16 rows against 64 take 366 vs 402 us at T=128, 638 vs 642 us at
+# T=256, 1153 vs 1103 us at T=512.
+MOE_MXFP4_BLOCK16_MAX = int(os.environ.get("CMLS_MOE_MXFP4_BLOCK16_MAX",
+                                           "256"))
+
+
+def _mxfp4_expert_dims(x8, w13_scale, ids):
+    """(H, I, E, k): the tiled buffers carry padded sizes only, so E and I
+    come from the row scales w13_scale [E, 2I]."""
+    return (x8.shape[1], w13_scale.shape[1] // 2, w13_scale.shape[0],
+            ids.shape[1])
+
+
+def _check_moe_mxfp4_shapes(x8, w13_scale, ids) -> None:
+    """The fused mxfp4 kernel's shape contract, held on the loop path too."""
+    h, inter, e, k = _mxfp4_expert_dims(x8, w13_scale, ids)
+    if h % 128 or inter % 128 or not (k <= e <= MOE_MAX_EXPERTS):
+        raise RuntimeError(
+            "moe_experts_mxfp4: need H % 128 == 0, I % 128 == 0 and k <= E "
+            "<= {}, got H={} I={} E={} k={}".format(
+                MOE_MAX_EXPERTS, h, inter, e, k))
+
+
+def _moe_experts_mxfp4_ref(x8, x_scale, w13_t, w13_e8t, w13_scale, w2_t,
+                           w2_e8t, w2_scale, ids, weights):
+    """fp32 per-expert loop over the dequantised operands; silu(g)*u is
+    rounded to bf16 and then quantised per row, as the fused path stores it."""
+    t = x8.shape[0]
+    h, inter, n_exp, k = _mxfp4_expert_dims(x8, w13_scale, ids)
+    xf = _dequant_fp8(x8, x_scale)
+    y = torch.zeros(t, k, h, dtype=torch.float32, device=x8.device)
+    for e in range(n_exp):
+        tok, choice = (ids == e).nonzero(as_tuple=True)
+        if tok.numel() == 0:
+            continue
+        w13 = dequant_mxfp4(*untile_mxfp4_weight(w13_t[e], w13_e8t[e],
+                                                 2 * inter, h), w13_scale[e])
+        w2 = dequant_mxfp4(*untile_mxfp4_weight(w2_t[e], w2_e8t[e], h, inter),
+                           w2_scale[e])
+        gu = xf[tok] @ w13.t()
+        act = torch.nn.functional.silu(gu[:, :inter]) * gu[:, inter:]
+        a8, a_scale = _quant_fp8_ref(act.to(torch.bfloat16))
+        y[tok, choice] = _dequant_fp8(a8, a_scale) @ w2.t()
+    out = torch.zeros(t, h, dtype=torch.float32, device=x8.device)
+    for j in range(k):  # ascending j, fp32, one rounding at the end
+        out += weights[:, j, None].float() * y[:, j]
+    return out.to(torch.bfloat16)
+
+
+def _moe_experts_mxfp4_loop(x8, x_scale, w13_t, w13_e8t, w13_scale, w2_t,
+                            w2_e8t, w2_scale, ids, weights):
+    """Prefill-sized GPU path: per expert, dequant_mxfp4_bf16 turns that
+    expert's tiles into a transient bf16 weight (one expert at a time), and
+    bf16 matmuls run on the e4m3 rows converted to bf16 (exact), the row
+    scale applied in fp32 after; silu_mul_fp8 sits between the two GEMMs.
+    Reads the row sets back to the host: not capturable. Agrees with the
+    fused path to fp8 tolerance, not bit for bit."""
+    t = x8.shape[0]
+    h, inter, n_exp, k = _mxfp4_expert_dims(x8, w13_scale, ids)
+    f8, bf = torch.float8_e4m3fn, torch.bfloat16
+    x8 = x8.view(torch.uint8)
+    y = torch.zeros(t, k, h, dtype=torch.float32, device=x8.device)
+    for e in range(n_exp):
+        tok, choice = (ids == e).nonzero(as_tuple=True)
+        if tok.numel() == 0:
+            continue
+        w13 = dequant_mxfp4_bf16(w13_t[e], w13_e8t[e], w13_scale[e],
+                                 2 * inter, h)
+        gu = ((x8[tok].view(f8).to(bf) @ w13.t()).float()
+              * x_scale[tok, None]).to(bf)
+        del w13
+        g8, g_scale = silu_mul_fp8(gu[:, :inter].contiguous(),
+                                   gu[:, inter:].contiguous())
+        w2 = dequant_mxfp4_bf16(w2_t[e], w2_e8t[e], w2_scale[e], h, inter)
+        y[tok, choice] = ((g8.view(f8).to(bf) @ w2.t()).float()
+                          * g_scale[:, None])
+        del w2
+    out = torch.zeros(t, h, dtype=torch.float32, device=x8.device)
+    for j in range(k):
+        out += weights[:, j, None] * y[:, j]
+    return out.to(torch.bfloat16)
+
+
+def moe_experts_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor,
+                      w13_t: torch.Tensor, w13_e8t: torch.Tensor,
+                      w13_scale: torch.Tensor, w2_t: torch.Tensor,
+                      w2_e8t: torch.Tensor, w2_scale: torch.Tensor,
+                      ids: torch.Tensor, weights: torch.Tensor,
+                      block_m: Optional[int] = None) -> torch.Tensor:
+    """moe_experts with e4m3 activations and MXFP4 expert weights -> bf16
+    [T, H].
+
+    x8: e4m3 bytes [T, H] with fp32 row scales x_scale [T] (ops.rmsnorm_fp8 /
+    ops.quant_fp8). Each expert's [2I, H] gate/up and [H, I] down matrix is
+    quantised by quantize_mxfp4 and kept only in the tile_mxfp4_weight
+    layout: w13_t uint8 [E, 2I/16, H/128, 64, 16] with e8m0 scales w13_e8t
+    [E, 2I/16, ceil(H/512), 64, 4], w2_t [E, H/16, I/128, 64, 16] with
+    w2_e8t [E, H/16, ceil(I/512), 64, 4], and fp32 row scales w13_scale
+    [E, 2I], w2_scale [E, H] (models/quant.py quantize_experts_mxfp4: all
+    ones). ids, weights as in moe_experts.
+
+    Reference semantics (CPU path): every operand dequantised to fp32
+    (untile_mxfp4_weight + dequant_mxfp4 per expert), the per-expert loop of
+    moe_experts, with silu(g)*u rounded to bf16 and then quantised per row
+    (_quant_fp8_ref) before the down projection; the sum over j in fp32 in
+    ascending j, one final rounding.
+
+    GPU: H % 128 == 0, I % 128 == 0, k <= E <= 64, contiguous
+    16-byte-aligned operands, else RuntimeError. A call with T <=
+    MOE_MXFP4_FUSED_MAX, and every call under graph capture, runs the fused
+    path (csrc/moe_mxfp4.hip: align, grouped block-scaled-MFMA gate/up GEMM,
+    row quantisation, grouped down GEMM, combine; sync-free), with row block
+    16 up to MOE_MXFP4_BLOCK16_MAX tokens and 64 above; ``block_m`` forces
+    the fused path and its row block. Both thresholds started from the fp8
+    values (256 and 64) and were moved by the mxfp4 table in
+    profiles/moe_bench.txt. Larger eager calls run a per-expert loop
+    (dequant_mxfp4_bf16 of one expert at a time + bf16 matmuls).
+
+    Bit-reproducibility, batch invariance and row-block independence hold
+    within the fused path, as for moe_experts_fp8; the loop agrees with it
+    to fp8 tolerance only, not bit for bit. PRECONDITION: ids in [0, E), as
+    for moe_experts.
+    """
+    args = (x8, x_scale, w13_t, w13_e8t, w13_scale, w2_t, w2_e8t, w2_scale,
+            ids, weights)
+    if x8.is_cuda:
+        ext = _require_ext("moe_experts_mxfp4")
+        if ext is not None:
+            t = x8.shape[0]
+            if block_m is None:
+                if (t > MOE_MXFP4_FUSED_MAX
+                        and not torch.cuda.is_current_stream_capturing()):
+                    _check_moe_mxfp4_shapes(x8, w13_scale, ids)
+                    return _moe_experts_mxfp4_loop(*args)
+                block_m = 16 if t <= MOE_MXFP4_BLOCK16_MAX else 64
+            return ext.moe_experts_mxfp4(*args, int(block_m))
+    return _moe_experts_mxfp4_ref(*args)
+
+
 def moe_ffn(x: torch.Tensor, router_weight: torch.Tensor, w13: torch.Tensor,
             w2: torch.Tensor, top_k: int,
             renormalize: bool = True) -> torch.Tensor:

@@ -86,6 +86,12 @@ torch::Tensor moe_experts_fp8(torch::Tensor x8, torch::Tensor x_scale,
                               torch::Tensor w2_8, torch::Tensor w2_scale,
                               torch::Tensor ids, torch::Tensor weights,
                               int64_t block_m);
+torch::Tensor moe_experts_mxfp4(torch::Tensor x8, torch::Tensor x_scale,
+                                torch::Tensor w13_t, torch::Tensor w13_e8t,
+                                torch::Tensor w13_scale, torch::Tensor w2_t,
+                                torch::Tensor w2_e8t, torch::Tensor w2_scale,
+                                torch::Tensor ids, torch::Tensor weights,
+                                int64_t block_m);
 void qk_rope_kv(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                 torch::Tensor positions, torch::Tensor inv_freq,
                 double attn_factor, c10::optional<torch::Tensor> q_norm_w,
@@ -167,6 +173,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x_scale"), py::arg("w13_8"), py::arg("w13_scale"),
         py::arg("w2_8"), py::arg("w2_scale"), py::arg("ids"),
         py::arg("weights"), py::arg("block_m") = 16);
+  m.def("moe_experts_mxfp4", &moe_experts_mxfp4, py::arg("x8"),
+        py::arg("x_scale"), py::arg("w13_t"), py::arg("w13_e8t"),
+        py::arg("w13_scale"), py::arg("w2_t"), py::arg("w2_e8t"),
+        py::arg("w2_scale"), py::arg("ids"), py::arg("weights"),
+        py::arg("block_m") = 16);
   m.def("qk_rope_kv", &qk_rope_kv, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("positions"), py::arg("inv_freq"),
         py::arg("attn_factor") = 1.0, py::arg("q_norm_w") = py::none(),
