@@ -501,12 +501,89 @@ def bench_mxfp4(results):
             del graphs
 
 
+# MX matrix peak for an e4m3 x e2m1 product: v_mfma_scale_f32_16x16x128_f8f6f4
+# with an 8-bit operand issues in 8 passes (32 cycles) for 2*16*16*128 FLOP,
+# x 4 SIMDs x 256 CUs x 2.4 GHz = 5.03 PFLOP/s (the CDNA4 ISA guide's pass
+# count; the MI355X data sheet's dense MXFP8 figure). HBM3E: 8 TB/s.
+MX_PEAK_FLOPS = 2 * 16 * 16 * 128 / 32 * 4 * 256 * 2.4e9
+HBM_BYTES_PER_S = 8e12
+
+
+def bench_mxfp4_gemm(results):
+    """ops.gemm_mxfp4 (csrc/mxfp4_gemm.hip; the default tile and both forced
+    ones) at the Llama-3-8B projection shapes and prefill-sized M against
+    what Mxfp4Linear.forward_q did before it: dequant_mxfp4_bf16 + bf16
+    matmul + fp32 row scaling + the cast back. As bench_mxfp4: each side
+    over weight clones exceeding the 256 MiB last-level cache, captured into
+    its own graph, graphs replayed alternately, median of three rounds with
+    min-max. us is per call; TFLOP/s from 2*M*N*K; the kernel's share of its
+    bound, the larger of FLOP over the MX peak and compulsory bytes (A,
+    weight tiles, C) over HBM bandwidth, with the binding one named."""
+    from clearml_serving_amd.models.quant import F8
+
+    shapes = (("qkv", 6144, 4096), ("o_proj", 4096, 4096),
+              ("gate_up", 28672, 4096), ("down", 4096, 14336))
+    for name, n, k in shapes:
+        w4, e8, rs = ops.quantize_mxfp4(torch.randn(n, k, device="cuda") / 32)
+        w4t, e8t = ops.tile_mxfp4_weight(w4, e8)
+        del w4, e8
+        mx_bytes = w4t.numel() + e8t.numel()
+        mx = [(w4t.clone(), e8t.clone())
+              for _ in range(max(8, -(-(300 << 20) // mx_bytes)))]
+        for m in (128, 512, 2048, 8192):
+            x8, xs = ops.quant_fp8(torch.randn(m, k, device="cuda",
+                                               dtype=torch.bfloat16))
+
+            def dequant_route(wt, et):
+                wd = ops.dequant_mxfp4_bf16(wt, et, rs, n, k)
+                return ((x8.view(F8).to(torch.bfloat16) @ wd.t()).float()
+                        * xs[:, None]).to(torch.bfloat16)
+
+            def tiled(tile):
+                return lambda: [ops.gemm_mxfp4(x8, xs, wt, et, rs, tile=tile)
+                                for wt, et in mx[:8]]
+
+            sides = {"gemm_mxfp4": tiled(0), "gemm_mxfp4_t64": tiled(64),
+                     "gemm_mxfp4_t128": tiled(128),
+                     "mxfp4_dequant+mm": lambda: [dequant_route(wt, et)
+                                                  for wt, et in mx[-8:]]}
+            graphs, iters = {}, {}
+            for side, fn in sides.items():
+                fn()
+                torch.cuda.synchronize()
+                graphs[side] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[side]):
+                    fn()
+                once = timeit(graphs[side].replay, iters=2, warmup=1)
+                iters[side] = int(min(100, max(3, 0.1 / once)))
+            runs = {}
+            for _ in range(3):
+                for side, graph in graphs.items():
+                    runs.setdefault(side, []).append(
+                        timeit(graph.replay, iters=iters[side], warmup=2) / 8)
+            flops = 2.0 * m * n * k
+            t_flop = flops / MX_PEAK_FLOPS
+            t_byte = (m * k + mx_bytes + 2.0 * m * n) / HBM_BYTES_PER_S
+            for side in graphs:
+                lo, dt, hi = sorted(runs[side])
+                r = dict(op=side, shape="{} M={} [{:.1f}-{:.1f}us]".format(
+                    name, m, lo * 1e6, hi * 1e6), us=dt * 1e6,
+                    tflops=flops / dt / 1e12)
+                if side != "mxfp4_dequant+mm":
+                    r["shape"] += " {:.0%} of {} bound".format(
+                        max(t_flop, t_byte) / dt,
+                        "MX-peak" if t_flop >= t_byte else "HBM")
+                results.append(r)
+            del graphs
+
+
 BENCHES = {"attention": bench_attention, "decode": bench_decode,
            "memops": bench_memops, "gemm": bench_gemm,
            "sampling": bench_sampling, "lora": bench_lora,
            "guided": bench_guided, "moe": bench_moe,
            "sample_rows": bench_sample_rows,
-           "qk_rope_kv": bench_qk_rope_kv, "mxfp4": bench_mxfp4}
+           "qk_rope_kv": bench_qk_rope_kv, "mxfp4": bench_mxfp4,
+           "mxfp4_gemm": bench_mxfp4_gemm}
 
 
 def main():

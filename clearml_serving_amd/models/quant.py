@@ -18,11 +18,15 @@ vLLM (preprocess_service.py:619-1095).
 ``{"quantization": "mxfp4"}`` (llama-family models) halves the weight bytes
 again: OCP MX e2m1 weights with an e8m0 scale per 32 k-values, taken
 directly by the gfx950 block-scaled MFMA against the same fused fp8
-activations (Mxfp4Linear, ops/csrc/mxfp4_path.hip). Expert stacks of a
+activations, for decode-shaped rows (ops/csrc/mxfp4_path.hip) and for
+prefill-shaped ones (ops/csrc/mxfp4_gemm.hip: workgroup tiles, A through
+LDS) on the one tiled copy of the weight (Mxfp4Linear). Expert stacks of a
 mixture-of-experts model are quantised the same way, one expert at a time,
 and kept only in the kernel-tiled layout (quantize_experts_mxfp4,
 ops.moe_experts_mxfp4, ops/csrc/moe_mxfp4.hip).
 """
+
+import os
 
 import torch
 import torch.nn as nn
@@ -153,18 +157,27 @@ class Mxfp4Linear(nn.Module):
     and the same bias handling. Only the kernel-tiled copy of the weight
     (ops.tile_mxfp4_weight) lives in HBM: 4.25 bits per weight.
 
-    Routing: decode-shaped rows on eligible shapes (K % 128 == 0,
-    N % 16 == 0) run ops.skinny_gemm_mxfp4, the block-scaled MFMA kernel.
-    Everything else -- larger M, other shapes (e.g. TP shards), CPU tensors
-    -- dequantises the whole weight to a transient bf16 [N, K] buffer
-    (ops.dequant_mxfp4_bf16: 2 bytes per weight written and read back, and
-    N*K*2 bytes of peak memory per call) and runs a bf16 matmul on the
-    dequantised activations. A tiled mxfp4 prefill kernel is out of scope."""
+    Routing, all on the block-scaled MFMA and the same buffers:
+    - "skinny": M <= SKINNY_MAX_M on K % 128 == 0, N % 16 == 0 runs
+      ops.skinny_gemm_mxfp4 (decode).
+    - "tiled": larger M, up to TILED_MAX_M, on K % 128 == 0, N % 128 == 0
+      runs ops.gemm_mxfp4 (prefill, chunked prefill, speculation
+      verification, large decode batches). CMLS_MXFP4_TILED=0 turns this
+      route off. A CPU tensor on this route takes the op's CPU path, one
+      fp32 product: the oracle of the kernel.
+    - "dequant": everything else -- other shapes (e.g. TP shards), M above
+      TILED_MAX_M, every other CPU tensor -- dequantises the whole weight
+      to a transient bf16 [N, K] buffer (ops.dequant_mxfp4_bf16: 2 bytes
+      per weight written and read back, and N*K*2 bytes of peak memory per
+      call) and runs a bf16 matmul on the dequantised activations."""
 
     # largest M at which skinny_gemm_mxfp4 beats the dequant + matmul route
     # on every Llama-3-8B projection shape (profiles/mxfp4_kernels.txt: at
     # M=64 12-60 us against 46-195 us); 64 is also the kernel's own limit
     SKINNY_MAX_M = 64
+    # largest M at which gemm_mxfp4 beat the dequant + matmul route on every
+    # Llama-3-8B projection shape (profiles/mxfp4_gemm.txt); None = no limit
+    TILED_MAX_M = None
 
     def __init__(self, linear: nn.Linear):
         super().__init__()
@@ -185,14 +198,28 @@ class Mxfp4Linear(nn.Module):
         n, k = self.out_features, self.in_features
         if m <= self.SKINNY_MAX_M and k % 128 == 0 and n % 16 == 0:
             return "skinny"
+        if (m > self.SKINNY_MAX_M and k % 128 == 0 and n % 128 == 0
+                and (self.TILED_MAX_M is None or m <= self.TILED_MAX_M)
+                and os.environ.get("CMLS_MXFP4_TILED", "1") != "0"):
+            return "tiled"
         return "dequant"
 
     def forward_q(self, x8: torch.Tensor, x_scale: torch.Tensor,
                   out_dtype=None) -> torch.Tensor:
         out_dtype = out_dtype or self.out_dtype
-        if x8.is_cuda and self._route(x8.shape[0]) == "skinny":
+        route = self._route(x8.shape[0])
+        # a CPU tensor on the "tiled" route takes gemm_mxfp4's CPU path, one
+        # fp32 product: the CPU's bf16 matmul below does not keep an fp32 sum
+        # over a long K and is no oracle for the kernel at K = 1024. Decode
+        # shapes on the CPU stay where they were
+        if route == "skinny" and not x8.is_cuda:
+            route = "dequant"
+        if route == "skinny":
             out = ops.skinny_gemm_mxfp4(x8, x_scale, self.weight_mx,
                                         self.scale_mx, self.weight_scale)
+        elif route == "tiled":
+            out = ops.gemm_mxfp4(x8, x_scale, self.weight_mx, self.scale_mx,
+                                 self.weight_scale)
         else:
             w = ops.dequant_mxfp4_bf16(self.weight_mx, self.scale_mx,
                                        self.weight_scale, self.out_features,

@@ -360,6 +360,40 @@ def skinny_gemm_mxfp4(a8: torch.Tensor, a_scale: torch.Tensor,
     return (a @ w.t()).to(torch.bfloat16)
 
 
+# CUs of the MI355X: gemm_mxfp4 takes 64-row tiles while 128-row tiles would
+# leave some of them without a workgroup (profiles/mxfp4_gemm.txt)
+GEMM_MXFP4_CUS = 256
+
+
+def gemm_mxfp4(a8: torch.Tensor, a_scale: torch.Tensor, w4t: torch.Tensor,
+               e8t: torch.Tensor, w_scale: torch.Tensor,
+               tile: int = 0) -> torch.Tensor:
+    """C[M,N] = (A8*s_a) @ (dequant(W4,E8)*s_w)^T -> bf16 for any M >= 1,
+    K % 128 == 0, N % 128 == 0 (N = len(w_scale), K = a8.shape[1]); w4t / e8t
+    in tile_mxfp4_weight layout: the prefill-shaped companion of
+    skinny_gemm_mxfp4 on the same buffers (csrc/mxfp4_gemm.hip). One
+    workgroup per ``tile`` x 128 outputs, A staged through swizzled LDS,
+    no split-K: a row's result does not depend on M or on the tile, and the
+    launch is capture-safe. tile=0 takes 64 rows while the 128-row grid has
+    fewer workgroups than CUs, else 128."""
+    m, k = a8.shape
+    n = w_scale.numel()
+    if k % 128 or n % 128 or m < 1:
+        raise ValueError("gemm_mxfp4: need M >= 1, K % 128 == 0 and "
+                         "N % 128 == 0, got M={} K={} N={}".format(m, k, n))
+    if a8.is_cuda:
+        ext = _require_ext("gemm_mxfp4")
+        if ext is not None:
+            if not tile:
+                tile = 64 if -(-m // 128) * (n // 128) < GEMM_MXFP4_CUS \
+                    else 128
+            return ext.gemm_mxfp4(a8.view(torch.uint8), a_scale, w4t, e8t,
+                                  w_scale, tile)
+    w = dequant_mxfp4(*untile_mxfp4_weight(w4t, e8t, n, k), w_scale)
+    a = a8.view(torch.float8_e4m3fn).float() * a_scale[:, None]
+    return (a @ w.t()).to(torch.bfloat16)
+
+
 def dequant_mxfp4_bf16(w4t: torch.Tensor, e8t: torch.Tensor,
                        w_scale: torch.Tensor, n: int, k: int) -> torch.Tensor:
     """Tiled mxfp4 weight (* w_scale) -> bf16 [N, K] (any N, K % 32 == 0):

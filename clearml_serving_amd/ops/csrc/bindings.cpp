@@ -52,6 +52,9 @@ torch::Tensor skinny_gemm_mxfp4(torch::Tensor a8, torch::Tensor a_scale,
                                 torch::Tensor w_scale, int64_t waves);
 torch::Tensor dequant_mxfp4_bf16(torch::Tensor w4t, torch::Tensor e8t,
                                  torch::Tensor w_scale, int64_t n, int64_t k);
+torch::Tensor gemm_mxfp4(torch::Tensor a8, torch::Tensor a_scale,
+                         torch::Tensor w4t, torch::Tensor e8t,
+                         torch::Tensor w_scale, int64_t tile);
 torch::Tensor conv3x3_nhwc(torch::Tensor x, torch::Tensor w,
                            c10::optional<torch::Tensor> bias, bool relu,
                            c10::optional<torch::Tensor> residual);
@@ -144,6 +147,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm_fp8_v2", &skinny_gemm_fp8_v2);
   m.def("skinny_gemm_mxfp4", &skinny_gemm_mxfp4);
   m.def("dequant_mxfp4_bf16", &dequant_mxfp4_bf16);
+  m.def("gemm_mxfp4", &gemm_mxfp4);
   m.def("conv3x3_nhwc", &conv3x3_nhwc, py::arg("x"), py::arg("w"),
         py::arg("bias") = py::none(), py::arg("relu") = false,
         py::arg("residual") = py::none());

@@ -39,16 +39,12 @@
 //       per four k-steps, op_sel = j. Padding scales are 127, padding
 //       elements 0.
 #include "common.h"
+#include "mxfp4_tiles.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 typedef __attribute__((ext_vector_type(4))) float mx_f32x4_t;
-
-constexpr int MX_NT = 16;      // N columns per workgroup
-constexpr int MX_KSTEP = 128;  // k per MFMA
-constexpr int MX_QUAD = 4;     // k-steps per packed scale dword
-constexpr int MX_SCALE_ONE = 0x7f7f7f7f;  // e8m0 2^0 in every byte
 
 // one k-step: B operand from the 16-byte weight line, A fragments straight
 // from global memory (2 x 16 B per lane per 16-row tile; rows >= M are
@@ -231,26 +227,6 @@ __attribute__((target("no-packed-fp32-ops"))) void dequant_mxfp4_bf16_kernel(
 
 #ifndef CMLS_KERNEL_ONLY
 namespace {
-
-void check_mx_tiles(const torch::Tensor& w4t, const torch::Tensor& e8t,
-                    const torch::Tensor& w_scale, int N, int K,
-                    const char* op) {
-  TORCH_CHECK(w4t.scalar_type() == at::kByte && e8t.scalar_type() == at::kByte,
-              op, ": tiled weights and scales are uint8");
-  TORCH_CHECK(w4t.is_contiguous() && e8t.is_contiguous() &&
-              w_scale.is_contiguous());
-  TORCH_CHECK(w_scale.scalar_type() == at::kFloat && w_scale.numel() == N,
-              op, ": w_scale is fp32 [N]");
-  const long nbs = (N + MX_NT - 1) / MX_NT;
-  const long nsteps = (K + MX_KSTEP - 1) / MX_KSTEP;
-  const long nquads = (nsteps + MX_QUAD - 1) / MX_QUAD;
-  TORCH_CHECK(w4t.numel() == nbs * nsteps * 64 * 16, op,
-              ": w4t is not the tiling of [", N, ", ", K, "]");
-  TORCH_CHECK(e8t.numel() == nbs * nquads * 64 * 4, op,
-              ": e8t is not the tiling of [", N, ", ", K, "]");
-  TORCH_CHECK((uintptr_t)w4t.data_ptr() % 16 == 0 &&
-              (uintptr_t)e8t.data_ptr() % 4 == 0, op, ": misaligned tiles");
-}
 
 template <int NW>
 void launch_skinny_mxfp4(const torch::Tensor& a8, const torch::Tensor& a_scale,
