@@ -218,8 +218,12 @@ def bench_moe(results):
     both row blocks and its per-expert scaled_mm loop; quantised to MXFP4
     (csrc/moe_mxfp4.hip, 0.53125 bytes per weight: e2m1 + an e8m0 scale per
     32) they give the mxfp4 rows: ops.moe_experts_mxfp4 fused at both row
-    blocks and its per-expert dequant + bf16 matmul loop. Every fused row is
-    also timed as a graph replay at T <= 64."""
+    blocks and its per-expert dequant + bf16 matmul loop, and
+    moe_mxfp4_tiled, the 128-row tiled kernels of csrc/moe_mxfp4_gemm.hip
+    (block_m=128), with the fraction of the 5.03 PF e4m3 x e2m1 peak that
+    its 2 * T*k * 3*I*H flop reach. Every fused row is also timed as a graph
+    replay at T <= 64. T = 4096 and 8192 leave out the bf16 and fp8 fused
+    rows (decode-shaped kernels, seconds per call there)."""
     h, inter, e, k = 4096, 14336, 8, 2
     g = torch.Generator().manual_seed(0)
     w13 = (torch.randn(e, 2 * inter, h, generator=g) * h ** -0.5
@@ -234,7 +238,7 @@ def bench_moe(results):
     from clearml_serving_amd.models.quant import quantize_experts_mxfp4
 
     mx = quantize_experts_mxfp4(w13) + quantize_experts_mxfp4(w2)
-    for t in (1, 8, 32, 64, 128, 256, 512, 2048):
+    for t in (1, 8, 32, 64, 128, 256, 512, 2048, 4096, 8192):
         x = torch.randn(t, h, generator=g).to(torch.bfloat16).cuda()
         ids, wts = ops.moe_route(torch.randn(t, e, generator=g).cuda(), k)
         hit = int(ids.unique().numel())
@@ -260,7 +264,12 @@ def bench_moe(results):
                 x8, xs, *mx, ids, wts, block_m=64)),
             ("moe_mxfp4_loop", lambda: ops._moe_experts_mxfp4_loop(
                 x8, xs, *mx, ids, wts)),
+            ("moe_mxfp4_tiled", lambda: ops.moe_experts_mxfp4(
+                x8, xs, *mx, ids, wts, block_m=128)),
         ]
+        if t > 2048:
+            cases = [c for c in cases
+                     if "mxfp4" in c[0] or c[0].endswith("_loop")]
         if t <= 64:
             for op, fn in [c for c in cases if "fused" in c[0]]:
                 side = torch.cuda.Stream()
@@ -285,6 +294,10 @@ def bench_moe(results):
                       else bytes_moved)
             results.append(dict(op=op, shape=shape, us=dt * 1e6,
                                 gbps=nbytes / dt / 1e9))
+            if op == "moe_mxfp4_tiled":
+                flops = 2.0 * t * k * 3 * inter * h
+                results[-1]["shape"] += " {:.1%} of MX-peak".format(
+                    flops / dt / 5.03e15)
 
 
 def bench_sample_rows(results):

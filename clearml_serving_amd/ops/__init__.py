@@ -1495,19 +1495,27 @@ def moe_experts_fp8(x8: torch.Tensor, x_scale: torch.Tensor,
 
 # --------------------------------------------------------------------- #
 # Mixture of experts with MXFP4 expert weights (kernels:
-# csrc/moe_mxfp4.hip)
+# csrc/moe_mxfp4.hip, csrc/moe_mxfp4_gemm.hip)
 # --------------------------------------------------------------------- #
-# Path threshold of moe_experts_mxfp4. It started at MOE_FP8_FUSED_MAX (256);
-# the mxfp4 table in profiles/moe_bench.txt has the fused path ahead of the
-# loop (which pays one expert's dequantisation to bf16 per expert and call)
-# at every measured T: 642 vs 3207 us at T=256, 4070 vs 4857 us at T=2048,
-# the largest T measured, so the threshold stands there.
-MOE_MXFP4_FUSED_MAX = int(os.environ.get("CMLS_MOE_MXFP4_FUSED_MAX", "2048"))
-# Row block of the fused mxfp4 path; it started at MOE_BLOCK16_MAX (64). Same
-# table: 16 rows against 64 take 366 vs 402 us at T=128, 638 vs 642 us at
-# T=256, 1153 vs 1103 us at T=512.
+# Path thresholds of moe_experts_mxfp4 (_moe_mxfp4_path), all from the
+# "tiled" table of profiles/moe_bench.txt (Mixtral-8x7B layer shape).
+# Largest eager T off the per-expert loop (which pays one expert's
+# dequantisation to bf16 per expert and call). It stood at 2048 while the
+# 64-row fused kernels were the alternative; the tiled path beats the loop at
+# T=2048, 4096 and 8192 (1239 vs 4830, 2479 vs 6495, 4302 vs 10237 us), so
+# the default is unbounded and the loop runs only where the variable asks.
+MOE_MXFP4_FUSED_MAX = int(os.environ.get("CMLS_MOE_MXFP4_FUSED_MAX",
+                                         str(2 ** 62)))
+# Row block of the fused mxfp4 path below MOE_MXFP4_TILED_MIN; it started at
+# MOE_BLOCK16_MAX (64). 16 rows against 64 take 368 vs 401 us at T=128, 645
+# vs 642 us at T=256, 1158 vs 1105 us at T=512.
 MOE_MXFP4_BLOCK16_MAX = int(os.environ.get("CMLS_MOE_MXFP4_BLOCK16_MAX",
                                            "256"))
+# Smallest T on the 128-row tiled kernels: the smallest measured T from which
+# they beat both fused row blocks at it and at every larger T. Tiled against
+# the better fused block: 262 vs 235 us at T=64, 287 vs 368 us at T=128, 302
+# vs 642 us at T=256, 367 vs 1105 us at T=512, 1239 vs 4077 us at T=2048.
+MOE_MXFP4_TILED_MIN = int(os.environ.get("CMLS_MOE_MXFP4_TILED_MIN", "128"))
 
 
 def _mxfp4_expert_dims(x8, w13_scale, ids):
@@ -1587,6 +1595,22 @@ def _moe_experts_mxfp4_loop(x8, x_scale, w13_t, w13_e8t, w13_scale, w2_t,
     return out.to(torch.bfloat16)
 
 
+_MOE_MXFP4_BLOCK_M = {"fused16": 16, "fused64": 64, "tiled": 128}
+
+
+def _moe_mxfp4_path(t: int, capturing: bool) -> str:
+    """Path of a moe_experts_mxfp4 call of t tokens that names no block_m:
+    "loop" (eager only: it reads row sets back to the host), "tiled" (128-row
+    blocks, csrc/moe_mxfp4_gemm.hip), "fused16" or "fused64" (csrc/
+    moe_mxfp4.hip). A captured call past MOE_MXFP4_FUSED_MAX cannot take the
+    loop and runs the tiled kernels, not the 64-row fused ones."""
+    if t > MOE_MXFP4_FUSED_MAX and not capturing:
+        return "loop"
+    if t >= MOE_MXFP4_TILED_MIN:
+        return "tiled"
+    return "fused16" if t <= MOE_MXFP4_BLOCK16_MAX else "fused64"
+
+
 def moe_experts_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor,
                       w13_t: torch.Tensor, w13_e8t: torch.Tensor,
                       w13_scale: torch.Tensor, w2_t: torch.Tensor,
@@ -1612,19 +1636,27 @@ def moe_experts_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor,
     ascending j, one final rounding.
 
     GPU: H % 128 == 0, I % 128 == 0, k <= E <= 64, contiguous
-    16-byte-aligned operands, else RuntimeError. A call with T <=
-    MOE_MXFP4_FUSED_MAX, and every call under graph capture, runs the fused
-    path (csrc/moe_mxfp4.hip: align, grouped block-scaled-MFMA gate/up GEMM,
-    row quantisation, grouped down GEMM, combine; sync-free), with row block
-    16 up to MOE_MXFP4_BLOCK16_MAX tokens and 64 above; ``block_m`` forces
-    the fused path and its row block. Both thresholds started from the fp8
-    values (256 and 64) and were moved by the mxfp4 table in
-    profiles/moe_bench.txt. Larger eager calls run a per-expert loop
-    (dequant_mxfp4_bf16 of one expert at a time + bf16 matmuls).
+    16-byte-aligned operands, else RuntimeError. Every GPU path is align,
+    grouped block-scaled-MFMA gate/up GEMM with the SwiGLU epilogue, row
+    quantisation, grouped down GEMM, combine; sync-free and capturable.
+    _moe_mxfp4_path picks the GEMM kernels: from MOE_MXFP4_TILED_MIN tokens
+    on the tiled ones (csrc/moe_mxfp4_gemm.hip: 128 sorted slots x 128
+    columns per workgroup, activations gathered through LDS), below it the
+    fused ones (csrc/moe_mxfp4.hip: one row block x 16 columns, split-K over
+    8 waves) with row block 16 up to MOE_MXFP4_BLOCK16_MAX tokens and 64
+    above. ``block_m`` = 16, 64 or 128 forces the fused kernels at that row
+    block or (128) the tiled ones; block_m=128 also refuses activation
+    matrices of 4 GiB or more. An eager call with T > MOE_MXFP4_FUSED_MAX
+    runs a per-expert loop instead (dequant_mxfp4_bf16 of one expert at a
+    time + bf16 matmuls, host reads); the default is unbounded, so the loop
+    runs only where CMLS_MOE_MXFP4_FUSED_MAX is set, and a captured call
+    past it takes the tiled kernels. The thresholds are read from the mxfp4
+    tables in profiles/moe_bench.txt.
 
-    Bit-reproducibility, batch invariance and row-block independence hold
-    within the fused path, as for moe_experts_fp8; the loop agrees with it
-    to fp8 tolerance only, not bit for bit. PRECONDITION: ids in [0, E), as
+    Bit-reproducibility and batch invariance hold within the fused path
+    (either row block gives the same bits) and within the tiled path, as for
+    moe_experts_fp8; the two accumulate K in different orders and agree to
+    fp8 tolerance only, as does the loop. PRECONDITION: ids in [0, E), as
     for moe_experts.
     """
     args = (x8, x_scale, w13_t, w13_e8t, w13_scale, w2_t, w2_e8t, w2_scale,
@@ -1632,13 +1664,13 @@ def moe_experts_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor,
     if x8.is_cuda:
         ext = _require_ext("moe_experts_mxfp4")
         if ext is not None:
-            t = x8.shape[0]
             if block_m is None:
-                if (t > MOE_MXFP4_FUSED_MAX
-                        and not torch.cuda.is_current_stream_capturing()):
+                path = _moe_mxfp4_path(
+                    x8.shape[0], torch.cuda.is_current_stream_capturing())
+                if path == "loop":
                     _check_moe_mxfp4_shapes(x8, w13_scale, ids)
                     return _moe_experts_mxfp4_loop(*args)
-                block_m = 16 if t <= MOE_MXFP4_BLOCK16_MAX else 64
+                block_m = _MOE_MXFP4_BLOCK_M[path]
             return ext.moe_experts_mxfp4(*args, int(block_m))
     return _moe_experts_mxfp4_ref(*args)
 

@@ -46,6 +46,17 @@
 // fp8_path.hip: per-row absmax quantisation to e4m3, {bytes [R, C], scale [R]}
 std::vector<torch::Tensor> quant_fp8(torch::Tensor x);
 
+// moe_mxfp4_gemm.hip: the same five stages with 128-row blocks and the tiled
+// GEMM kernel; operands already checked by moe_experts_mxfp4 below
+torch::Tensor moe_experts_mxfp4_tiled(torch::Tensor x8, torch::Tensor x_scale,
+                                      torch::Tensor w13_t,
+                                      torch::Tensor w13_e8t,
+                                      torch::Tensor w13_scale,
+                                      torch::Tensor w2_t, torch::Tensor w2_e8t,
+                                      torch::Tensor w2_scale,
+                                      torch::Tensor ids,
+                                      torch::Tensor weights);
+
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
@@ -335,14 +346,18 @@ torch::Tensor moe_experts_mxfp4(torch::Tensor x8, torch::Tensor x_scale,
               "moe_experts_mxfp4: H must be a multiple of 128, got ", h);
   TORCH_CHECK(inter % KSTEP == 0 && inter >= KSTEP && inter <= INT_MAX,
               "moe_experts_mxfp4: I must be a multiple of 128, got ", inter);
-  TORCH_CHECK(block_m == 16 || block_m == 64,
-              "moe_experts_mxfp4: block_m must be 16 or 64, got ", block_m);
+  TORCH_CHECK(block_m == 16 || block_m == 64 || block_m == 128,
+              "moe_experts_mxfp4: block_m must be 16, 64 or 128, got ",
+              block_m);
   check_scale(x_scale, x8, t, "x_scale");
   check_scale(w13_scale, x8, e * 2 * inter, "w13_scale");
   check_scale(w2_scale, x8, e * h, "w2_scale");
   check_aligned16(x8, "x8");
   check_tiles(w13_t, w13_e8t, x8, e, 2 * inter, h, "w13");
   check_tiles(w2_t, w2_e8t, x8, e, h, inter, "w2");
+  if (block_m == 128)  // prefill-shaped: 128 x 128 tiles through LDS
+    return moe_experts_mxfp4_tiled(x8, x_scale, w13_t, w13_e8t, w13_scale,
+                                   w2_t, w2_e8t, w2_scale, ids, weights);
 
   torch::Tensor sorted_slots, block_expert;
   cmls_moe::launch_align(ids, e, block_m, sorted_slots, block_expert);
