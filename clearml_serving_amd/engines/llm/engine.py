@@ -597,6 +597,7 @@ class LlmEngine:
                       "preemptions": 0, "aborts": 0,
                       "graph_captures": 0, "graph_replays": 0,
                       "spec_proposed": 0, "spec_accepted": 0,
+                      "spec_verify_multi": 0,
                       "lora_requests": 0, "swa_blocks_freed": 0}
         # multi-LoRA: models.lora.LoraBank built by start() when
         # cfg.lora_modules is set; None = every path below runs as before
@@ -1825,12 +1826,43 @@ class LlmEngine:
         }
         if "lora" in plan:
             self._lora_ctx(attn_ctx, plan["lora"], lens, smax)
+        if self._verify_attn_route(b, smax, max(plan["kv_lens"])):
+            # the layers send this forward's attention through
+            # ops.attention_decode_multi where the head shape allows
+            attn_ctx["verify"] = True
         rows = [i * smax + j for i in range(b) for j in range(lens[i])]
         last_idx = torch.tensor(rows, dtype=torch.long, device=dev)
-        return self.model(tokens.view(-1).to(dev),
-                          positions.view(-1).to(dev),
-                          kv_caches=self.kv_caches, attn_ctx=attn_ctx,
-                          last_token_idx=last_idx, gather_logits=False)
+        logits = self.model(tokens.view(-1).to(dev),
+                            positions.view(-1).to(dev),
+                            kv_caches=self.kv_caches, attn_ctx=attn_ctx,
+                            last_token_idx=last_idx, gather_logits=False)
+        if attn_ctx.get("verify_multi"):
+            self.stats["spec_verify_multi"] += 1
+        return logits
+
+    @staticmethod
+    def _verify_attn_route(batch: int, seq: int, max_kv_len: int) -> bool:
+        """Whether a verify forward of ``batch`` sequences, ``seq`` padded
+        query tokens and at most ``max_kv_len`` keys takes the multi-query
+        split-KV attention kernel instead of the chunked-prefill kernel.
+
+        Rule: the new kernel is the default only in the (batch, context,
+        seq) region where benchmarks/verify_attn_bench.py measured its
+        median below the paged-prefill kernel's in the same run.
+        CMLS_VERIFY_ATTN=1 forces it everywhere, CMLS_VERIFY_ATTN=0
+        restores the old route everywhere."""
+        flag = os.environ.get("CMLS_VERIFY_ATTN", "")
+        if flag in ("0", "1"):
+            return flag == "1"
+        # Measured (profiles/verify_attn_bench.txt, H=32 Hkv=8 D=128, bf16
+        # and fp8 KV): B in {1, 4, 8} x context in {32, 128, 1k, 4k, 16k} x
+        # seq in {2, 5, 8}. No crossover inside the sweep: multi/paged is
+        # below one at every point, closest to one at the short end and
+        # falling with context (the chunk kernel walks the context serially
+        # per query head). The sweep bounds the batch, so larger batches
+        # keep the old kernel until they are measured; ``seq`` is bounded by
+        # the kernel itself (verify_attn_supported in models/llama.py).
+        return batch <= 8
 
     # -------------------- decode hipGraph capture --------------------- #
     # A llama-8B decode step dispatches ~350 kernels from Python; at B=64

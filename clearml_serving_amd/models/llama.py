@@ -69,6 +69,17 @@ class LlamaConfig:
         return bool(self.rope_scaling) or self.qk_norm
 
 
+def verify_attn_supported(seq: int, heads: int, kv_heads: int,
+                          head_dim: int) -> bool:
+    """Shapes ops.attention_decode_multi serves (attention_verify.hip): up
+    to 8 query tokens per sequence, GQA group up to 8, head_dim 64 or 128.
+    Anything else (num_spec_tokens above 7, say) keeps the chunk kernel."""
+    return (1 <= seq <= ops.DECODE_MULTI_MAX_Q
+            and heads % kv_heads == 0
+            and heads // kv_heads <= ops.DECODE_MULTI_MAX_GQ
+            and head_dim in (64, 128))
+
+
 class LlamaLayer(nn.Module):
     def __init__(self, cfg: LlamaConfig, tp_rank: int = 0, tp_size: int = 1,
                  layer_idx: int = 0):
@@ -223,7 +234,15 @@ class LlamaLayer(nn.Module):
             # chunked prefill: this chunk's queries attend to the full paged
             # history (K/V of the chunk were just scattered into the cache)
             b, s = attn_ctx["batch"], attn_ctx["seq"]
-            ctx = ops.attention_prefill_paged(
+            # speculative verification (engine sets "verify"): a few query
+            # tokens per sequence take the split-KV multi-query kernel;
+            # chunked prefill and unsupported shapes keep the chunk kernel
+            attend = ops.attention_prefill_paged
+            if attn_ctx.get("verify") and verify_attn_supported(
+                    s, self.heads, self.kv_heads, self.head_dim):
+                attend = ops.attention_decode_multi
+                attn_ctx["verify_multi"] = True  # engine stats
+            ctx = attend(
                 q.unflatten(0, (b, s)), k_cache, v_cache,
                 attn_ctx["block_table"], attn_ctx["kv_lens"],
                 attn_ctx["q_lens"], scale=scale, k_scale=k_sc, v_scale=v_sc,

@@ -651,6 +651,44 @@ def attention_decode(
     return out
 
 
+DECODE_MULTI_MAX_Q = 8    # query tokens per sequence (attention_verify.hip)
+DECODE_MULTI_MAX_GQ = 8   # query heads per kv head
+
+
+def attention_decode_multi(
+    q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+    block_table: torch.Tensor, kv_lens: torch.Tensor, q_lens: torch.Tensor,
+    scale: Optional[float] = None,
+    k_scale: Optional[torch.Tensor] = None,
+    v_scale: Optional[torch.Tensor] = None,
+    window: Optional[int] = None,
+) -> torch.Tensor:
+    """Paged-KV decode attention with SEVERAL query tokens per sequence
+    (speculative verification): q [B, Sq, H, D] with 1 <= Sq <= 8 and a GQA
+    group H / H_kv of at most 8. Arguments, masking and result are those of
+    :func:`attention_prefill_paged` -- the two are interchangeable by
+    contract; this one is the split-KV kernel (attention_verify.hip) that
+    reads K/V once per kv head for all Sq * H / H_kv query rows."""
+    sq, hq, hkv = q.shape[1], q.shape[2], k_cache.shape[1]
+    if not 1 <= sq <= DECODE_MULTI_MAX_Q:
+        raise ValueError("attention_decode_multi: 1..{} query tokens per "
+                         "sequence, got {}".format(DECODE_MULTI_MAX_Q, sq))
+    if hq % hkv or hq // hkv > DECODE_MULTI_MAX_GQ:
+        raise ValueError("attention_decode_multi: GQA group must be 1..{}, "
+                         "got {}/{}".format(DECODE_MULTI_MAX_GQ, hq, hkv))
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    window = _check_window(window)
+    if q.is_cuda:
+        ext = _require_ext("attention_decode_multi")
+        if ext is not None:
+            return ext.attention_decode_multi(
+                q, k_cache, v_cache, block_table, kv_lens, q_lens,
+                float(scale), k_scale, v_scale, window)
+    return attention_prefill_paged(q, k_cache, v_cache, block_table, kv_lens,
+                                   q_lens, scale, k_scale, v_scale, window)
+
+
 def kv_cache_write(
     k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor,
     v_cache: torch.Tensor, slot_mapping: torch.Tensor,

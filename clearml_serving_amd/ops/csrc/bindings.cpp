@@ -36,6 +36,11 @@ torch::Tensor attention_prefill_paged(
     torch::Tensor block_table, torch::Tensor kv_lens, torch::Tensor q_lens,
     double scale, c10::optional<torch::Tensor> k_scale,
     c10::optional<torch::Tensor> v_scale, int64_t window);
+torch::Tensor attention_decode_multi(
+    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+    torch::Tensor block_table, torch::Tensor kv_lens, torch::Tensor q_lens,
+    double scale, c10::optional<torch::Tensor> k_scale,
+    c10::optional<torch::Tensor> v_scale, int64_t window);
 void rope_inplace(torch::Tensor q, torch::Tensor k, torch::Tensor positions,
                   double theta);
 std::vector<torch::Tensor> rmsnorm_fp8(torch::Tensor x, torch::Tensor weight,
@@ -135,6 +140,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm", &skinny_gemm, py::arg("a"), py::arg("w"),
         py::arg("variant") = 0);
   m.def("attention_prefill_paged", &attention_prefill_paged, py::arg("q"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
+        py::arg("kv_lens"), py::arg("q_lens"), py::arg("scale"),
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(),
+        py::arg("window") = 0);
+  m.def("attention_decode_multi", &attention_decode_multi, py::arg("q"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
         py::arg("kv_lens"), py::arg("q_lens"), py::arg("scale"),
         py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(),
